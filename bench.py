@@ -15,6 +15,9 @@ the timed region (weak scaling).  If the box has fewer devices than ranks (a 1-G
 2-rank logic check) the ranks share devices and the collective falls back to gloo, because RCCL refuses
 two ranks on one device; the JSON line says so (`"collective"`).
 
+`--dump-outputs DIR` (rank 0) saves the [B] scores of the last timed step (all ranks' shards, in rank order) as
+DIR/scores.npy: weights, prompts and pixels are seeded, so the same arguments give the same inputs on every run.
+
 Output (rank 0): ONE JSON line of at most 4 KB (`short_line`; tests/test_bench_line.py holds it to that) — the contract
 keys, `roofline`, `cpu_baseline` and one scalar per side leg — printed last on stdout; every leg's full record goes to
 `bench_detail.json` beside this file (and to gpurun_out/ when that directory exists).  Legs (tools/bench_legs.py), all
@@ -249,6 +252,9 @@ def parse_args(argv=None):
                     help="bracket every kernel of every N-th timed step with HIP events (each pair costs "
                          "~3 us of stream serialisation: all steps = -2.3 %% throughput, every 4th = -0.6 %%)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full record goes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/scores.npy "
+                         "(float32 [n_gpus * batch], rank order; inputs are seeded, so two builds compare output for output)")
     args = ap.parse_args(argv)
     args.harness_kv = {}
     for kv in filter(None, args.harness.split(",")):
@@ -404,6 +410,12 @@ def main():
         prof = net.profile_read()
         net.profile(False)
     assert torch.isfinite(scores).all()
+    if args.dump_outputs and rank == 0:   # before the sustained leg reuses scores[]
+        import numpy as np
+
+        last = full.view(ws, args.steps, B)[:, -1] if coll else scores[-1]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), last.reshape(-1).float().cpu().numpy())
     nb_cpu = min(args.cpu_batch, B)
     first_scores = scores[0][:nb_cpu].clone()  # step 0 scored bufs[0]; the sustained leg overwrites scores[]
     leg_done("timed_steps")

@@ -16,6 +16,10 @@ What is captured
                      T=1 and T=2, under the four shims of SURVEY.md §8c.
   measures.npz       the reference's get_measures (utils/detection_util.py:108-119) on
                      synthetic score sets incl. ties and the SURVEY KAT.
+  bank_data/         the reference's class-name data files (data/ImageNet/imagenet_class_clean.npy,
+                     data/ImageNet/imagenet_class_index.json, data/ImageNet100/class_list.txt), copied as
+                     they are, and imagenet_templates.json: the 80 prompt templates of its
+                     utils/imagenet_templates.py as plain strings (`python make_golden.py banks`).
 """
 from __future__ import annotations
 
@@ -318,9 +322,27 @@ def capture_concept_banks():
         json.dump(banks, f, indent=1)
 
 
+def capture_bank_data():
+    """The data files behind the ImageNet100 / ImageNet-1k banks, and the reference's 80 prompt templates (each
+    lambda applied to the literal "{c}"), so that the host-contract tests need no copy of the reference."""
+    import json
+    import shutil
+
+    out = os.path.join(HERE, "bank_data")
+    for rel in ("ImageNet/imagenet_class_clean.npy", "ImageNet/imagenet_class_index.json", "ImageNet100/class_list.txt"):
+        os.makedirs(os.path.join(out, os.path.dirname(rel)), exist_ok=True)
+        shutil.copyfile(os.path.join("/root/reference/data", rel), os.path.join(out, rel))
+    spec = importlib.util.spec_from_file_location("ref_templates", "/root/reference/utils/imagenet_templates.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(os.path.join(out, "imagenet_templates.json"), "w") as f:
+        json.dump([t("{c}") for t in mod.openai_imagenet_template], f, indent=1)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "banks":
         capture_concept_banks()
+        capture_bank_data()
         sys.exit(0)
     ref = load_reference_detection_util()
     capture_measures(ref)

@@ -144,3 +144,9 @@ def test_an_oversized_record_loses_sections_not_the_measurement():
     back = json.loads(out)
     assert back["value"] > 0 and back["roofline"]["frac"] > 0 and back["cpu_baseline"]["value"] > 0
     assert "arms" in back["dropped_for_length"] and "arms" not in back
+
+
+def test_dump_outputs_is_off_unless_asked_and_steps_are_the_timed_count():
+    assert bench.parse_args([]).dump_outputs is None
+    a = bench.parse_args(["--dump-outputs", "out", "--steps", "7", "--warmup", "2", "--quick"])
+    assert a.dump_outputs == "out" and a.steps == 7 and a.warmup == 2   # --quick leaves the step counts alone

@@ -25,13 +25,13 @@ def _affine_state(geo):
     return sd
 
 
-# mcm_debug_ln_row(1 / 2): W one / two K-steps ahead; 3 / 4: the same with W in the blocked (piece-contiguous) layout
+# mcm_debug_ln_row(1 / 2): W one / two K-steps ahead; 3 / 4: the same with W in the blocked (piece-contiguous) layout.
+# Three W stages fit in LDS at N = 768 only (160 KiB); at N = 1024 (ViT-L/14) a 3-stage request runs the 2-stage kernel,
+# and is held to the same results as every other case.
 @pytest.mark.parametrize("stages", [1, 2, 3, 4], ids=["2-stage", "3-stage", "2-stage-blockedW", "3-stage-blockedW"])
 @pytest.mark.parametrize("ckpt,precision,batch", [("ViT-B/16", "fp16", 160), ("ViT-B/16", "bf16", 512),
                                                    ("ViT-L/14", "fp16", 64), ("ViT-B/32", "fp16", 512), ("ViT-B/16", "fp16", 3)])
 def test_full_row_tiles_equal_the_launched_layernorms_to_round_off(ckpt, precision, batch, stages):
-    if stages in (2, 4) and ckpt == "ViT-L/14":
-        pytest.skip("three W stages need N = 768 (160 KiB of LDS); N = 1024 runs two")
     geo = geometry(ckpt)
     sd = _affine_state(geo)
     ids, _ = make_token_ids(40, seed=2)

@@ -1,5 +1,6 @@
 """Host-side pieces of the drop-in boundary that need no GPU: concept banks vs the reference's own
-(tests/golden/concept_banks.json, written by make_golden.py from /root/reference), the `--templates`
+(tests/golden/concept_banks.json, written by make_golden.py from the reference; the class-name data files
+and prompt templates they come from are stored under tests/golden/bank_data/), the `--templates`
 reader, the CLI's flag surface, the folder index order."""
 import hashlib
 import json
@@ -24,12 +25,11 @@ def test_hardcoded_banks_equal_the_reference(golden_dir, ds):
 
 @pytest.mark.parametrize("ds", ["ImageNet100", "ImageNet"])
 def test_file_banks_equal_the_reference(golden_dir, ds):
-    """Needs the reference's data/ directory (class-name files are dataset artefacts, not shipped)."""
+    """The class-name files are dataset artefacts, not shipped with the package: the reference's copies are
+    stored in tests/golden/bank_data/ in its data/ layout."""
     from utils.common import get_test_labels
 
-    data = "/root/reference/data"
-    if not os.path.isdir(data):
-        pytest.skip("reference data/ directory not present on this box")
+    data = os.path.join(golden_dir, "bank_data")
     got = [str(x) for x in get_test_labels(types.SimpleNamespace(in_dataset=ds, data_dir=data))]
     want = _banks(golden_dir)
     assert len(got) == want[ds + "_n"] and got[:3] == want[ds + "_first3"]
@@ -47,7 +47,7 @@ def test_missing_bank_files_warn_or_raise(tmp_path):
         get_test_labels(a)
 
 
-def test_read_templates(tmp_path):
+def test_read_templates(tmp_path, golden_dir):
     from mcm_amd.detection import read_templates
 
     txt = tmp_path / "t.txt"
@@ -61,10 +61,16 @@ def test_read_templates(tmp_path):
     bad.write_text("no placeholder here\n")
     with pytest.raises(ValueError):
         read_templates(str(bad))
-    ref = "/root/reference/utils/imagenet_templates.py"
-    if os.path.exists(ref):  # the 80 OpenAI templates the reference ships as data (BASELINE config 5)
-        t = read_templates(ref)
-        assert len(t) == 80 and t[0] == "a bad photo of a {c}." and all("{c}" in x for x in t)
+    # the 80 OpenAI templates the reference ships as data (BASELINE config 5), laid out as its
+    # utils/imagenet_templates.py lays them out: one list of lambdas, then a dict of subsets repeating entries
+    want = json.load(open(os.path.join(golden_dir, "bank_data", "imagenet_templates.json")))
+    ref = tmp_path / "imagenet_templates.py"
+    ref.write_text("openai_imagenet_template = [\n" + "".join(f"    lambda c: f'{x}',\n" for x in want) + "]\n\n\n"
+                   "openai_imagenet_template_subset = {\n    0: [\n"
+                   + "".join(f"    lambda c: f'{x}',\n" for x in want[:5]) + "    ],\n}\n")
+    t = read_templates(str(ref))
+    assert t == want
+    assert len(t) == 80 and t[0] == "a bad photo of a {c}." and all("{c}" in x for x in t)
 
 
 def test_cli_flags_and_ckpt_mapping(tmp_path, monkeypatch):
