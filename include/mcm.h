@@ -382,8 +382,13 @@ int mcm_op_layernorm_split(mcm_handle* h, const float* x_dev, const float* gamma
 int mcm_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                            int32_t heads, void* stream);
 /* Multi-head SDPA (modeling_clip.py:259-277,313-331): qkv [nseq*seq_len, 3*heads*64]
- * packed as [q | k | v], head_dim 64, scale 0.125; causal != 0 for the text tower;
- * seq_len ≤ 288.  out [nseq*seq_len, heads*64]. */
+ * packed as [q | k | v], head_dim 64, scale 0.125; causal != 0 for the text tower.
+ * out [nseq*seq_len, heads*64].  Two routes, chosen by length:
+ *   seq_len ≤ 288 (18 key tiles of 16): K and V of a head held whole in LDS (the B/32, B/16 and L/14 towers, causal text);
+ *   seq_len 289 ... 1025, bidirectional only: K and V streamed through LDS in 64-key tiles with an online softmax (every mode,
+ *   mcm_op_attention_split too; ViT-L/14@336px: 577 tokens).
+ * A bidirectional seq_len above 1025 (the vision-token ceiling of mcm_create) is refused; causal attention (the text tower's
+ * 77 tokens) has the first route only. */
 int mcm_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev,
                      int32_t nseq, int32_t seq_len, int32_t heads, int32_t causal,
                      void* stream);

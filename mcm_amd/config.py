@@ -163,11 +163,16 @@ CHECKPOINTS = {
     "ViT-B/16": ClipGeometry("ViT-B/16", patch_size=16),
     "ViT-L/14": ClipGeometry("ViT-L/14", patch_size=14, v_width=1024, v_heads=16, v_layers=24,
                              v_mlp=4096, t_width=768, t_heads=12, t_mlp=3072, proj_dim=768),
+    # not a reference choice: OpenAI's strongest CLIP, L/14 at 336 px (24 x 24 patches + CLS = 577 vision tokens, past the
+    # 288 that keep K and V of a head in LDS: the streaming attention kernel)
+    "ViT-L/14@336px": ClipGeometry("ViT-L/14@336px", image_size=336, patch_size=14, v_width=1024, v_heads=16, v_layers=24,
+                                   v_mlp=4096, t_width=768, t_heads=12, t_mlp=3072, proj_dim=768),
 }
 HUB_IDS = {
     "ViT-B/32": "openai/clip-vit-base-patch32",
     "ViT-B/16": "openai/clip-vit-base-patch16",
     "ViT-L/14": "openai/clip-vit-large-patch14",
+    "ViT-L/14@336px": "openai/clip-vit-large-patch14-336",
 }
 
 # Reduced geometries for fast parity tests: full-width heads (head_dim 64) and every code

@@ -18,7 +18,9 @@
 //   fp32 VALU kernel; both with exact expf.
 // The round-1 kernel (attn_bf16_kernel: V transposed while staged through registers) exists in the
 // harness build only (-DMCM_HARNESS), as the A/B arm of tests/test_gpu_kernels.py.
-// Measurements: DESIGN.md section 4.2.
+// Bidirectional attention past 288 tokens (ViT-L/14@336px: 577) streams K / V through LDS instead: attn_long_kernel /
+// attn_long_f32_kernel below launch_tr_x2.
+// Measurements: DESIGN.md sections 4.2 and 4.6.
 #include "common.hpp"
 
 namespace {
@@ -1021,6 +1023,368 @@ hipError_t launch_tr_x2(const void* qkv, void* out, int nseq, int L, int heads, 
 }
 
 
+// ---- long sequences: K and V streamed through LDS (L = 289 ... 1025; ViT-L/14@336px: 577 tokens) --------------------------
+// The kernels above keep the whole K and V of a head in LDS, which ends at 18 key tiles (288 keys; 577 keys of fp16 K + V take
+// 148 KiB, of fp32 or split K + V 295 KiB).  Past that, flash-style: a workgroup = one (sequence, head, query chunk) of LONG_NW
+// 16-query blocks, one per wave; the keys arrive in tiles of LONG_KT = 64, double-buffered in LDS, and every wave keeps its
+// block's running max m, row sum l and O in registers.  A tile's step, in the textbook order (guide T13's safe order: the
+// decision covers the tile's P before any of it is exponentiated; no deferred rescale, no threshold):
+//   S^T = K·Q^T (the swapped product of attn_tr_kernel: a lane holds 4 keys of each 16-key subtile for ONE query), tile max,
+//   m' = max(m, tile max), a = exp2((m - m') SC) (0 on the first tile: m = -inf), O *= a, l *= a,
+//   P = exp2(S SC - m' SC) rounded to the operand format, l += rowsum(P) (all-ones MFMA), O^T += V^T·P^T (transpose reads).
+// O and l are scaled by the same a, so an error in a moves the weights of the earlier tiles against the later ones, like a logit
+// error of the same size: tests/online_softmax_budget.py adds those terms to the whole-row budget.
+// Tile j + 1 is fetched by LDS-DMA (glds16: an asm DMA that hipcc does not drain before the next ds_read) while tile j is
+// computed; one s_waitcnt vmcnt(0) + barrier per tile publishes it.  No inter-workgroup waits.  Same LDS images as attn_tr_kernel
+// (K: GEMM pair / XOR image, V: 32-B segments XORed with (key >> 1) & 3; tile bases are multiples of 64 keys, so the swizzles
+// of a tile's local rows are those of its global keys).  Keys past L are clamped to row L - 1 on the load and masked in S.
+// LDS: 16-bit 2 stages x (K + V) x 8 KiB = 32 KiB (several workgroups per CU); X2 (hi + lo images) 64 KiB.
+constexpr int LONG_MAX_L = 1025;  // 32^2 + 1: ViT-B/16 at 512 px, ViT-L/14 at 448 px
+constexpr int LONG_NW = 8;        // waves (16-query blocks) per workgroup
+constexpr int LONG_KT = 64;       // keys per streamed tile
+
+template <int PREC, bool X2>
+__global__ __launch_bounds__(LONG_NW * 64, 2) void attn_long_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
+                                                                    int L, int heads, int qrows, int nchunk, int rev, int hm) {
+  static_assert(!X2 || PREC == MCM_PREC_F16, "split activations: fp16");
+  enter_precision_mode<PREC>();
+  constexpr int IMG = LONG_KT * 128;              // one K or V image of a tile (bytes)
+  constexpr int PARTS = X2 ? 2 : 1;               // hi, (X2) lo
+  constexpr int STAGE = 2 * PARTS * IMG;          // [part][K, V][IMG]
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];   // static: the code object states the footprint
+  constexpr int NPW = 2 * PARTS * (IMG / 1024) / LONG_NW;   // 1-KiB DMA pieces per wave and tile
+  static_assert(NPW * LONG_NW * 1024 == STAGE, "pieces");
+  constexpr uint32_t ONE2 = PREC == MCM_PREC_F16 ? 0x3c003c00u : 0x3f803f80u;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bid = (rev & 1) ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int sh = bid / nchunk, chunk = bid - sh * nchunk;
+  const int seq = sh / heads, h = sh - seq * heads;
+  const int D = heads * 64;
+  const size_t rs = X2 ? (size_t)6 * D : MCM_HM(hm) ? (size_t)64 : (size_t)3 * D;
+  const size_t KO = X2 ? (size_t)2 * D : MCM_HM(hm) ? (size_t)heads * hm * 64 : (size_t)D, VO = 2 * KO;
+  const uint16_t* base = X2 ? qkv + (size_t)seq * L * rs + h * 128
+                            : MCM_HM(hm) ? qkv + ((size_t)h * hm + (size_t)seq * L) * 64 : qkv + (size_t)seq * L * rs + h * 64;
+  const int fr = lane & 15, g = lane >> 4;
+  const int qb = chunk * LONG_NW + wave;
+  const bool active = qb < (qrows + 15) / 16;     // wave-uniform: an idle wave still loads its share of every tile
+  const int q = qb * 16 + fr;
+  const int ntile = (L + LONG_KT - 1) / LONG_KT;
+
+  auto issue_tile = [&](int j) {
+    const uint32_t sb = lds_addr(smem) + (uint32_t)((j & 1) * STAGE);
+    const int k0 = j * LONG_KT;
+#pragma unroll
+    for (int i = 0; i < NPW; ++i) {
+      const int piece = wave * NPW + i;                            // [part][K, V][8 pieces]
+      const int part = piece >> 4, kind = (piece >> 3) & 1, blk = piece & 7;
+      const uint16_t* src;
+      if (kind == 0) {  // K: 8 key rows in the GEMM-style pair / XOR image
+        const int p = blk * 4 + (lane >> 4), sl = lane & 15;
+        const int row = 2 * p + (sl >> 3);
+        const int cc = (sl & 7) ^ (p & 7);
+        src = base + (size_t)min(k0 + row, L - 1) * rs + KO + part * 64 + cc * 8;
+      } else {          // V: 8 key rows, 32-B segments XORed with (key >> 1) & 3
+        const int row = blk * 8 + (lane >> 3), pc = lane & 7;
+        const int lc = ((((pc >> 1) ^ (row >> 1)) & 3) << 1) | (pc & 1);
+        src = base + (size_t)min(k0 + row, L - 1) * rs + VO + part * 64 + lc * 8;
+      }
+      glds16(src, sb + (uint32_t)((part * 2 + kind) * IMG + blk * 1024));
+    }
+  };
+
+  uint4 q0, q1, ql0 = make_uint4(0, 0, 0, 0), ql1 = ql0;
+  {
+    const uint16_t* qp = base + (size_t)min(q, L - 1) * rs + g * 8;
+    q0 = *(const uint4*)qp;
+    q1 = *(const uint4*)(qp + 32);
+    if constexpr (X2) {
+      ql0 = *(const uint4*)(qp + 64);
+      ql1 = *(const uint4*)(qp + 96);
+    }
+  }
+  issue_tile(0);
+  // Q is waited for here, once: left to hipcc, its vmcnt wait lands inside the tile loop, where it also drains the DMA of the
+  // next tile (hipcc cannot see the asm DMA) on every iteration
+  asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, q0)), "v"(__builtin_bit_cast(u32x4_t, q1)),
+               "v"(__builtin_bit_cast(u32x4_t, ql0)), "v"(__builtin_bit_cast(u32x4_t, ql1)));
+
+  int koff[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) koff[kk] = ktile_off(fr, kk * 4 + g);
+  int voff[4];
+  {
+    const int sw = (2 * g + (fr >> 3)) & 3;
+    const int vb = IMG + (4 * g + (fr >> 2)) * 128 + (fr & 3) * 8;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) voff[dt] = vb + ((dt ^ sw) << 5);
+  }
+  constexpr float SC = 0.125f * 1.4426950408889634f;  // scale * log2(e)
+  const f32x4_t zero = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  f32x4_t lacc = zero;
+  f32x4_t o[4] = {zero, zero, zero, zero};
+  float m = -INFINITY;
+
+  for (int j = 0; j < ntile; ++j) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile j have landed ...
+    __syncthreads();                                    // ... and everybody's; every wave is done with tile j - 1's stage
+    if (j + 1 < ntile) issue_tile(j + 1);
+    if (!active) continue;
+    const char* Ks = smem + (j & 1) * STAGE;
+    f32x4_t s[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint4 k0 = *(const uint4*)(Ks + t * 2048 + koff[0]), k1 = *(const uint4*)(Ks + t * 2048 + koff[1]);
+      if constexpr (X2) {  // the two cross terms first (small), then the leading one: one fp32 accumulator chain
+        const uint4 kl0 = *(const uint4*)(Ks + 2 * IMG + t * 2048 + koff[0]);
+        const uint4 kl1 = *(const uint4*)(Ks + 2 * IMG + t * 2048 + koff[1]);
+        s[t] = mfma_keep<PREC>(kl0, q0, zero);
+        s[t] = mfma_keep<PREC>(kl1, q1, s[t]);
+        s[t] = mfma_keep<PREC>(k0, ql0, s[t]);
+        s[t] = mfma_keep<PREC>(k1, ql1, s[t]);
+        s[t] = mfma_keep<PREC>(k0, q0, s[t]);
+        s[t] = mfma_keep<PREC>(k1, q1, s[t]);
+      } else {
+        s[t] = mfma_keep<PREC>(k0, q0, zero);
+        s[t] = mfma_keep<PREC>(k1, q1, s[t]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    float mt = -INFINITY;
+    const bool full = j * LONG_KT + LONG_KT <= L;      // uniform: only the last tile can hold keys past L
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (!full) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[t][r] = (j * LONG_KT + t * 16 + g * 4 + r < L) ? s[t][r] : -INFINITY;
+      }
+      mt = fmaxf(fmaxf(fmaxf(fmaxf(mt, s[t][0]), s[t][1]), s[t][2]), s[t][3]);
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float mn = fmaxf(m, mt);                     // finite: every tile holds at least one valid key
+    const float a = __builtin_amdgcn_exp2f((m - mn) * SC);   // exp2(-inf) = 0 on the first tile
+    m = mn;
+    lacc *= a;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] *= a;
+    const float msc = X2 ? mn * SC - 12.0f : mn * SC;  // X2: P scaled by 2^12 (attn_tr_kernel's header); cancels in O / l
+    uint2 pt[4], pl[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float e[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(fmaf(s[t][r], SC, -msc));
+      if constexpr (X2) {
+        split2<PREC>(e[0], e[1], pt[t].x, pl[t].x);
+        split2<PREC>(e[2], e[3], pt[t].y, pl[t].y);
+      } else {
+        pt[t] = make_uint2(pack2<PREC>(e[0], e[1]), pack2<PREC>(e[2], e[3]));
+        pl[t] = make_uint2(0u, 0u);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {  // two 32-key steps per tile: five independent accumulator chains
+      const uint4 pu = make_uint4(pt[2 * u].x, pt[2 * u].y, pt[2 * u + 1].x, pt[2 * u + 1].y);
+      const uint4 plu = make_uint4(pl[2 * u].x, pl[2 * u].y, pl[2 * u + 1].x, pl[2 * u + 1].y);
+      if constexpr (X2) lacc = mfma_keep<PREC>(make_uint4(ONE2, ONE2, ONE2, ONE2), plu, lacc);
+      lacc = mfma_keep<PREC>(make_uint4(ONE2, ONE2, ONE2, ONE2), pu, lacc);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const char* vp = Ks + voff[dt];
+        const uint2 lo = tr_read16(vp + (2 * u) * 2048), hi = tr_read16(vp + (2 * u + 1) * 2048);
+        if constexpr (X2) {  // V_lo P_hi and V_hi P_lo first, then the leading term
+          const uint2 llo = tr_read16(vp + 2 * IMG + (2 * u) * 2048), lhi = tr_read16(vp + 2 * IMG + (2 * u + 1) * 2048);
+          o[dt] = mfma_keep<PREC>(make_uint4(llo.x, llo.y, lhi.x, lhi.y), pu, o[dt]);
+          o[dt] = mfma_keep<PREC>(make_uint4(lo.x, lo.y, hi.x, hi.y), plu, o[dt]);
+        }
+        o[dt] = mfma_keep<PREC>(make_uint4(lo.x, lo.y, hi.x, hi.y), pu, o[dt]);
+      }
+    }
+  }
+  if (!active) return;
+  const float rl = 1.0f / lacc[0];
+  uint32_t pk[4][2], pkl[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    if constexpr (X2) {
+      split2<PREC>(o[dt][0] * rl, o[dt][1] * rl, pk[dt][0], pkl[dt][0]);
+      split2<PREC>(o[dt][2] * rl, o[dt][3] * rl, pk[dt][1], pkl[dt][1]);
+    } else {
+      pk[dt][0] = pack2<PREC>(o[dt][0] * rl, o[dt][1] * rl);
+      pk[dt][1] = pack2<PREC>(o[dt][2] * rl, o[dt][3] * rl);
+    }
+  }
+  uint4 wide[2], widel[2];
+#pragma unroll
+  for (int pr = 0; pr < 2; ++pr) {  // (attn_tr_kernel's store: a lane ends up with 8 consecutive dims of one 16-dim block)
+    const auto w0 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][0], pk[2 * pr + 1][0], false, false);
+    const auto w1 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][1], pk[2 * pr + 1][1], false, false);
+    wide[pr] = make_uint4(w0[0], w1[0], w0[1], w1[1]);
+    if constexpr (X2) {
+      const auto l0 = __builtin_amdgcn_permlane16_swap(pkl[2 * pr][0], pkl[2 * pr + 1][0], false, false);
+      const auto l1 = __builtin_amdgcn_permlane16_swap(pkl[2 * pr][1], pkl[2 * pr + 1][1], false, false);
+      widel[pr] = make_uint4(l0[0], l1[0], l0[1], l1[1]);
+    }
+  }
+  if (q < L) {
+    uint16_t* orow = X2 ? out + ((size_t)seq * L + q) * 2 * D + h * 128 : out + ((size_t)seq * L + q) * D + h * 64;
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {
+      *(uint4*)(orow + (2 * pr + (g & 1)) * 16 + (g & 2) * 4) = wide[pr];
+      if constexpr (X2) *(uint4*)(orow + 64 + (2 * pr + (g & 1)) * 16 + (g & 2) * 4) = widel[pr];
+    }
+  }
+}
+
+// Exact fp32 form (the parity arm): attn_f32_mfma_kernel's arithmetic (v_mfma_f32_16x16x4_f32, P in fp32, expf) with the same
+// streaming and online softmax.  K and V tiles are [64][68] fp32 rows (272 B: conflict-free b128 fragment reads), staged through
+// registers: tile j + 1's global loads are issued before tile j's arithmetic and written to the other stage after it (one
+// barrier per tile).  LDS: 2 stages x (K + V) x 17 KiB = 68 KiB.  The row sum stays a per-lane fp32 partial (scaled by the
+// same a as O) until the two cross-lane adds at the end.
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 2) void attn_long_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L,
+                                                                   int heads, int qrows, int nchunk, int rev) {
+  constexpr int RS = 68, IMG = LONG_KT * RS;       // floats
+  constexpr int NLD = LONG_KT * 16 / (NW * 64);     // float4 of each image per thread and tile
+  static_assert(NLD * NW * 64 == LONG_KT * 16, "loads");
+  __shared__ __attribute__((aligned(16))) float stage[2 * 2 * IMG];   // [2][K, V][IMG]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bid = (rev & 1) ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int sh = bid / nchunk, chunk = bid - sh * nchunk;
+  const int seq = sh / heads, h = sh - seq * heads;
+  const int D = heads * 64;
+  const size_t rs = (size_t)3 * D;
+  const float* base = qkv + (size_t)seq * L * rs + h * 64;
+  const int fr = lane & 15, g = lane >> 4;
+  const int qb = chunk * NW + wave;
+  const bool active = qb < (qrows + 15) / 16;
+  const int q = qb * 16 + fr;
+  const int ntile = (L + LONG_KT - 1) / LONG_KT;
+
+  f32x4_t kr[NLD], vr[NLD];
+  auto fetch = [&](int j) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = threadIdx.x + i * NW * 64, row = idx >> 4, c = (idx & 15) * 4;
+      const float* rp = base + (size_t)min(j * LONG_KT + row, L - 1) * rs + c;
+      kr[i] = *(const f32x4_t*)(rp + D);
+      vr[i] = *(const f32x4_t*)(rp + 2 * D);
+    }
+  };
+  auto stash = [&](int j) {
+    float* Ks = stage + (j & 1) * 2 * IMG;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = threadIdx.x + i * NW * 64, row = idx >> 4, c = (idx & 15) * 4;
+      *(f32x4_t*)(Ks + row * RS + c) = kr[i];
+      *(f32x4_t*)(Ks + IMG + row * RS + c) = vr[i];
+    }
+  };
+  float qv[16];
+  {
+    const float* qp = base + (size_t)min(q, L - 1) * rs + 16 * g;
+#pragma unroll
+    for (int j4 = 0; j4 < 4; ++j4) {
+      const f32x4_t t = *(const f32x4_t*)(qp + 4 * j4);
+      qv[4 * j4] = t[0]; qv[4 * j4 + 1] = t[1]; qv[4 * j4 + 2] = t[2]; qv[4 * j4 + 3] = t[3];
+    }
+  }
+  fetch(0);
+  stash(0);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(qv[i]));   // Q waited for once, not inside the loop behind the prefetch
+  __syncthreads();
+  f32x4_t o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, z = 0.f;
+  for (int j = 0; j < ntile; ++j) {
+    if (j + 1 < ntile) fetch(j + 1);
+    if (active) {
+      const float* Ks = stage + (j & 1) * 2 * IMG;
+      const float* Vs = Ks + IMG;
+      f32x4_t s[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float* kp = Ks + (t * 16 + fr) * RS + 16 * g;
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j4 = 0; j4 < 4; ++j4) {
+          const f32x4_t kk = *(const f32x4_t*)(kp + 4 * j4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[e], qv[4 * j4 + e], acc, 0, 0, 0);
+        }
+        s[t] = acc;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      float mt = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = j * LONG_KT + t * 16 + g * 4 + r < L;
+          s[t][r] = ok ? s[t][r] * 0.125f : -INFINITY;
+          mt = fmaxf(mt, s[t][r]);
+        }
+      }
+      mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      const float mn = fmaxf(m, mt);
+      const float a = expf(m - mn);   // (-inf - mn: 0)
+      m = mn;
+      z *= a;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] *= a;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = expf(s[t][r] - mn);
+          s[t][r] = e;
+          z += e;
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float* vp = Vs + (t * 16 + 4 * g + r) * RS + fr;
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[dt * 16], s[t][r], o[dt], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (j + 1 < ntile) stash(j + 1);   // the stage tile j - 1 used: every wave passed the previous barrier after reading it
+    __syncthreads();
+  }
+  z += __shfl_xor(z, 16, 64);
+  z += __shfl_xor(z, 32, 64);
+  if (active && q < L && q < qrows) {
+    const float rz = 1.0f / z;
+    float* orow = out + ((size_t)seq * L + q) * D + h * 64 + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) *(f32x4_t*)(orow + dt * 16) = o[dt] * rz;
+  }
+}
+
+// Grid: nseq x heads x query chunks (LONG_NW 16-query blocks each; qrows = 1, the CLS-only last layer, is one chunk).
+template <int PREC, bool X2>
+hipError_t launch_long(const void* qkv, void* out, int nseq, int L, int heads, int qrows, hipStream_t s, int rev, int hm) {
+  const int nqb = (qrows + 15) / 16, nchunk = (nqb + LONG_NW - 1) / LONG_NW;
+  const int64_t grid = (int64_t)nseq * heads * nchunk;
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if constexpr (PREC == MCM_PREC_F32)
+    hipLaunchKernelGGL((attn_long_f32_kernel<LONG_NW>), dim3((unsigned)grid), dim3(LONG_NW * 64), 0, s, (const float*)qkv,
+                       (float*)out, L, heads, qrows, nchunk, rev);
+  else
+    hipLaunchKernelGGL((attn_long_kernel<PREC, X2>), dim3((unsigned)grid), dim3(LONG_NW * 64), 0, s, (const uint16_t*)qkv,
+                       (uint16_t*)out, L, heads, qrows, nchunk, rev, hm);
+  return hipGetLastError();
+}
+
 
 // Waves per workgroup.  The q-blocks of a sequence are dealt round-robin to the waves, so the slowest wave has
 // ceil(q-blocks / waves) of them.  Measured at B/16 batch 512 / L/14 batch 256 (tools/attn_probe.py — removed in round 6 —, same
@@ -1069,6 +1433,23 @@ hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int 
                             bool causal, int qrows, hipStream_t s, bool reverse, int hm, bool split, unsigned int* fault) {
   if (nseq <= 0 || L <= 0 || heads <= 0) return hipErrorInvalidValue;
   if (qrows <= 0 || qrows > L) qrows = L;
+  // Bidirectional problems past 18 key tiles (L > 288): the streaming kernels (K / V through LDS, online softmax), every mode.
+  // Everything at L <= 288, and causal attention at any length, keeps the kernels below.
+  if (!causal && (L + 15) / 16 > 18) {
+    if (L > LONG_MAX_L) return hipErrorInvalidValue;
+    if (split) {
+      if (prec != MCM_PREC_F16 || hm) return hipErrorInvalidValue;
+      return launch_long<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, 0);
+    }
+    if (hm && (prec == MCM_PREC_F32 || (int64_t)hm < (int64_t)nseq * L)) return hipErrorInvalidValue;
+#ifndef MCM_HARNESS
+    if (hm) return hipErrorInvalidValue;  // head-major qkv: harness library only
+#endif
+    if (prec == MCM_PREC_F16) return launch_long<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, hm);
+    if (prec == MCM_PREC_BF16) return launch_long<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, hm);
+    if (prec == MCM_PREC_F32) return launch_long<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, 0);
+    return hipErrorInvalidValue;
+  }
   if (split) {  // split images in and out (GemmArgs::xsplit): fp16, bidirectional, row-major
     if (prec != MCM_PREC_F16 || causal || hm) return hipErrorInvalidValue;
     return launch_tr_x2(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0);

@@ -628,7 +628,8 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
     return fail(nullptr, MCM_EINVAL, "bad workspace bounds");
   {
     const int g = c.image_size / c.patch_size;
-    if (g * g + 1 > 288) return fail(nullptr, MCM_EINVAL, "more than 288 vision tokens");
+    // attention's ceiling (attention.hip LONG_MAX_L): 288 tokens keep K and V of a head in LDS, up to 1025 stream them
+    if (g * g + 1 > 1025) return fail(nullptr, MCM_EINVAL, "more than 1025 vision tokens");
   }
   hipError_t e = hipSetDevice(c.device);
   if (e != hipSuccess) return fail(nullptr, MCM_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
