@@ -21,7 +21,7 @@ DIR/scores.npy: weights, prompts and pixels are seeded, so the same arguments gi
 Output (rank 0): ONE JSON line of at most 4 KB (`short_line`; tests/test_bench_line.py holds it to that) — the contract
 keys, `roofline`, `cpu_baseline` and one scalar per side leg — printed last on stdout; every leg's full record goes to
 `bench_detail.json` beside this file (and to gpurun_out/ when that directory exists).  Legs (tools/bench_legs.py), all
-outside the timed region, N = 1 only:
+outside the timed region, N = 1 only, and only in a `--full` run (below: what a plain run keeps):
   roofline      GEMM kernel family: algorithmic FLOP ÷ HIP-event time of the launches of every 4th timed
                 step (`profiled_steps`; bracketing every launch of every step costs 2.3 % of throughput);
                 `traffic` from two rocprofv3 --pmc child passes of this script;
@@ -33,6 +33,11 @@ outside the timed region, N = 1 only:
   arms/configs  3 timed steps each of the other precision arms and of BASELINE configs 2 and 4 (K = 100; ViT-L/14);
   parity        AUROC / AUPR / FPR95 on config 3 of every native arm against the exact-fp32 arm and against the HF
                 CLIPModel fp32 reference on this device over the same pixels (mcm_amd/parity.py).
+
+A plain run (no `--full`) is what the headline needs and nothing more: set up, warm up, time the steps, write
+`--dump-outputs`, print the line.  Its `roofline` comes from the HIP events of the timed steps, with `traffic` read from the
+committed profiles/*_traffic.json.  `--full` adds the legs above (and `sustained`, which then runs on every rank); the
+`--no-*` options and `--quick` still switch single legs or all of them off within a `--full` run.
 """
 from __future__ import annotations
 
@@ -213,7 +218,11 @@ def parse_args(argv=None):
                          "fp16: one fp16 operand per weight is lossless) or as drawn (fp32-valued: the 16-bit arms then run "
                          "the split-weight GEMMs unless --weight-operands single)")
     ap.add_argument("--weight-operands", default="auto", choices=["auto", "single", "split"])
-    ap.add_argument("--quick", action="store_true", help="the timed region and its roofline only: every side leg off")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (CPU baseline, sustained, ingest, refined, live PMC traffic, other arms and "
+                         "configs, parity); without it a run is setup, warm-up, the timed steps and the line")
+    ap.add_argument("--quick", action="store_true",
+                    help="the timed region and its roofline only: every side leg off, --full or not")
     ap.add_argument("--cpu-seconds", type=float, default=120.0,
                     help="hard cap on the CPU baseline's timed part (it stops after 256 images); 0 disables it")
     ap.add_argument("--cpu-batch", type=int, default=64)
@@ -262,7 +271,7 @@ def parse_args(argv=None):
         if k not in HARNESS_KEYS:
             ap.error(f"unknown --harness key {k!r}")
         args.harness_kv[k] = int(v)
-    if args.quick:
+    if args.quick or not args.full:
         args.cpu_seconds = args.sustain_seconds = 0.0
         args.ingest = "none"
         args.no_live_traffic = args.no_arms = args.no_configs = args.no_refined = args.no_drift = True

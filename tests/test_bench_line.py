@@ -150,3 +150,19 @@ def test_dump_outputs_is_off_unless_asked_and_steps_are_the_timed_count():
     assert bench.parse_args([]).dump_outputs is None
     a = bench.parse_args(["--dump-outputs", "out", "--steps", "7", "--warmup", "2", "--quick"])
     assert a.dump_outputs == "out" and a.steps == 7 and a.warmup == 2   # --quick leaves the step counts alone
+
+
+def test_a_plain_run_has_no_side_legs_and_full_brings_them_back():
+    plain = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert plain.cpu_seconds == 0 and plain.sustain_seconds == 0 and plain.ingest == "none"
+    assert plain.no_drift and plain.no_arms and plain.no_configs and plain.no_refined and plain.no_live_traffic
+    assert not plain.no_profile and plain.profile_every == 4   # the timed steps are the same in both kinds of run
+    full = bench.parse_args(["--full"])
+    assert full.cpu_seconds == 120.0 and full.sustain_seconds == 5.0 and full.ingest == "host-u8,host-raw"
+    assert not (full.no_drift or full.no_arms or full.no_configs or full.no_refined or full.no_live_traffic)
+    assert not full.no_profile and full.profile_every == 4
+    some = bench.parse_args(["--full", "--no-arms", "--cpu-seconds", "0"])
+    assert some.no_arms and some.cpu_seconds == 0 and not some.no_configs and some.sustain_seconds == 5.0
+    q = bench.parse_args(["--full", "--quick"])
+    assert q.cpu_seconds == 0 and q.sustain_seconds == 0 and q.ingest == "none" and q.no_arms and q.no_drift

@@ -87,7 +87,7 @@ def test_bench_gpus_4_logic_on_one_device(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--ckpt", "tiny", "--batch", "48", "--prompts", "20",
-                        "--steps", "4", "--warmup", "1", "--sustain-seconds", "1.5", "--cpu-seconds", "0", "--ingest", "none",
+                        "--steps", "4", "--warmup", "1", "--full", "--sustain-seconds", "1.5", "--cpu-seconds", "0", "--ingest", "none",
                         "--no-arms", "--no-configs", "--no-refined", "--no-drift", "--no-live-traffic",
                         "--detail", detail],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

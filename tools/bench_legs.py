@@ -1,7 +1,7 @@
 """bench_legs.py — the side legs of bench.py: everything the benchmark reports NEXT TO the timed region (CPU baseline, parity
 against HF / the exact-fp32 arm, ingest rates, other arms and configurations, live PMC traffic, clock / power sampling).  None of
-it runs inside the timed region; bench.py imports it lazily on rank 0.  Moved out of bench.py in round 5 so that the benchmark
-proper (workload, timed loop, roofline, the one short JSON line) reads in one screen."""
+it runs inside the timed region, and only `bench.py --full` runs the legs; bench.py imports it lazily on rank 0.  Moved out
+of bench.py in round 5 so that the benchmark proper (workload, timed loop, roofline, the one short JSON line) reads in one screen."""
 from __future__ import annotations
 
 import json
