@@ -438,6 +438,10 @@ int mcm_debug_clear_faults(mcm_handle* h);
  * and the walk direction (reverse != 0: jobs in descending order). */
 int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                            int32_t heads, int32_t causal, int32_t qrows, int32_t reverse, void* stream);
+/* mcm_op_attention_split with the same two launch parameters: query rows (0 = all; 1 = the CLS-only last layer) and the walk
+ * direction. */
+int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                                 int32_t heads, int32_t qrows, int32_t reverse, void* stream);
 /* A/B and ablation bits of the GEMM kernels (gemm.hip, GemmArgs::dbg; 0 = shipped behaviour). */
 int mcm_debug_gemm_dbg(int32_t bits);
 /* A/B: run the QKV projection + attention of every layer per chunk of the batch (n chunks; 1 = shipped). */

@@ -1425,6 +1425,16 @@ int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, voi
   return MCM_OK;
 }
 
+// mcm_op_attention_split with the same two launch parameters (the split arm of the model passes qrows = 1 in the CLS-only last
+// layer and alternates the walk direction)
+int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                                 int32_t heads, int32_t qrows, int32_t reverse, void* stream) {
+  if (!h) return MCM_EINVAL;
+  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, false, qrows, (hipStream_t)stream,
+                              reverse != 0, 0, true));
+  return MCM_OK;
+}
+
 int mcm_debug_gemm_dbg(int32_t bits) {  // ablation / A-B bits of gemm.hip (GemmArgs::dbg)
   gemm_set_dbg(bits);
   return MCM_OK;

@@ -9,6 +9,9 @@ u32 = 2^-24 is the unit roundoff of fp32.  The one free constant is C_ACC, the m
 fp32 dot product may be off by.  It was chosen on the CPU (tests/test_error_budget.py::test_c_acc_covers_cpu_dot_products):
 a sequential fp32 dot product (the order of a chain of v_mfma_f32_* accumulating one K-step after another) and torch's
 CPU fp32 matmul stay below C_ACC / 2 at every K from 64 to 4096 on the tests' operand distributions.
+The split forms (split activations, split weights) run chains of 2K and 4K products in one fp32 accumulator (2 x 4096 at
+L/14 fc2, 4 x 3072 at B/16 fc2 with both split); C_ACC = 16 covers them unchanged: the kernel-order chain stays below
+6.6 u32 * sum |x||w| there (tests/test_error_budget.py::test_c_acc_covers_split_chains).
 """
 from __future__ import annotations
 
@@ -238,6 +241,202 @@ def score_budget(img, txt, T: float, kind: int):
         r = 2 * (dumax + eps_e) + 3 * U32
         bud = (2.0 / K) * r * (np.abs(p - 1.0 / K) * p).sum(axis=1)
     return ref, bud + 0.5 * ulp(ref, "fp32")
+
+
+# ---- split forms: one value as an fp16 pair hi + lo (split activations, split outputs, split weights) -------------------
+FP16_SAT = 65520.0    # the first |v| that rounds above 65504: what sat_report counts (common.hpp)
+U_SPLIT = 2.0 ** -22  # relative representation error of a split in fp16's normal range (split_repr)
+
+
+def f16_sat(a) -> np.ndarray:
+    """fp32 -> fp16 as v_cvt_pk_f16_f32 does it under MODE.FP16_OVFL (common.hpp enter_precision_mode): round to nearest
+    even, fp16 subnormals included; finite values beyond the range saturate to +-65504."""
+    a = np.asarray(a, np.float32)
+    with np.errstate(over="ignore"):
+        h = a.astype(np.float16)
+    return np.where(np.isinf(h) & np.isfinite(a), np.copysign(np.float16(FP16_MAX), a).astype(np.float16), h)
+
+
+def split2_f16(v):
+    """common.hpp split2<MCM_PREC_F16> bit for bit: hi = f16_sat(v), lo = f16_sat(v - hi), the difference taken in fp32
+    (exact below the range edge).  Returns (hi, lo) as float16 arrays."""
+    v = np.asarray(v, np.float32)
+    hi = f16_sat(v)
+    lo = f16_sat(v - hi.astype(np.float32))
+    return hi, lo
+
+
+def split_image(x) -> np.ndarray:
+    """fp32 [M, K] (K % 64 == 0) -> the split image [M, 2K] as float16 (split2_f16's bits): per 64 columns hi[64] then
+    lo[64]."""
+    x = np.asarray(x, np.float32)
+    M, K = x.shape
+    hi, lo = split2_f16(x)
+    out = np.empty((M, K // 64, 2, 64), np.float16)
+    out[:, :, 0, :] = hi.reshape(M, K // 64, 64)
+    out[:, :, 1, :] = lo.reshape(M, K // 64, 64)
+    return out.reshape(M, 2 * K)
+
+
+def image_parts(y):
+    """split image [M, 2N] (16-bit values in any float dtype) -> (hi, lo), each [M, N] float64."""
+    y = np.asarray(y)
+    M, N2 = y.shape
+    v = y.reshape(M, N2 // 128, 2, 64).astype(np.float64)
+    return v[:, :, 0, :].reshape(M, N2 // 2), v[:, :, 1, :].reshape(M, N2 // 2)
+
+
+def merge_image(y) -> np.ndarray:
+    """split image [M, 2N] -> hi + lo [M, N] (exact in fp64, returned as float64)."""
+    hi, lo = image_parts(y)
+    return hi + lo
+
+
+def split_repr(a) -> np.ndarray:
+    """Representation term of a split: |v - hi - lo| for any v with |v| <= a, i.e. 1/2 ulp16 of the remainder v - hi.
+    In fp16's normal range the remainder is at most 1/2 ulp16(v), so the term is 2^-22 |v| at the bottom of a binade and
+    2^-23 |v| at its top (U_SPLIT).  Below |v| = 2^-3 the remainder is under 2^-14 and lo lands on fp16's subnormal grid
+    (spacing 2^-24): an absolute floor of 2^-25.  Past the range edge hi saturates at 65504 (FP16_OVFL) and lo carries
+    v - 65504 at fp16 precision, up to 131008 (+ its half ulp); beyond that lo saturates as well: no bound (infinite)."""
+    a = np.abs(np.asarray(a, np.float64))
+    rem = np.where(a < FP16_MAX, 0.5 * ulp(a, "fp16"), np.maximum(a - FP16_MAX, 16.0))
+    return np.where(rem <= FP16_MAX + 16.0, 0.5 * ulp(rem, "fp16"), np.inf)
+
+
+def gemm_split_budget(lin, s, epi: int, out_split: bool, resid0=None, din=0.0):
+    """(ref, budget) of a split GEMM (mcm_op_linear_ex with MCM_LINEAR_SPLIT_X and / or SPLIT_W).
+
+    lin, s: gemm_reference on the MERGED operands (hi + lo, exact in fp64), as the other budgets use the operands as given.
+    Every pass of a logical K-step (X_hi W, X_lo W; with split weights four: X_hi W_hi, X_lo W_hi, X_hi W_lo, X_lo W_lo) is
+    one more stretch of the same fp32 MFMA chain, so the accumulation term is C_ACC u32 sum |x||w| over the merged operands
+    for a chain of 2K or 4K products (test_error_budget.py::test_c_acc_covers_split_chains).
+      epi 2: the fp32 residual, gemm_budget's rule;
+      epi 0 / 1 with a plain fp16 output (SPLIT_X without SPLIT_OUT): gemm_budget's fp16 rule (EPI_GELU: quick_gelu_fast);
+      out_split (EPI_STORE_X2 / EPI_GELU_X2): the fp32-grade value plus split_repr of the stored pair.  EPI_GELU_X2 runs the
+      exact QuickGELU of the fp32 arm, x / (1 + __expf(-1.702 x)) with an IEEE division: gemm_budget's fp32 GELU term (C_GELU
+      ulps of the result and the rounding of the exponent argument) covers it.
+    din: an error of the operands themselves, carried into lin (gemm_unsplit_budget)."""
+    lin = np.asarray(lin, np.float64)
+    acc = C_ACC * U32 * s + U32 * np.abs(lin) + din
+    if epi == 2:
+        ref = np.asarray(resid0, np.float64) + lin
+        return ref, ulp(ref, "fp32") + acc
+    if epi == 1:
+        ref = quick_gelu64(lin)
+        pre = GELU_DERIV * acc + U32 * np.abs(ref) * (C_GELU + 1.702 * np.abs(lin))
+    else:
+        ref, pre = lin, acc
+    if not out_split:
+        bud = 0.5 * ulp(np.abs(ref) + pre, "fp16") + pre
+        return ref, np.where(np.abs(ref) + pre < FP16_MAX, bud, np.inf)
+    bud = ulp(ref, "fp32") + pre
+    return ref, bud + split_repr(np.abs(ref) + bud)
+
+
+def gemm_unsplit_budget(x, w, bias, epi: int, out_split: bool, resid0=None, x_split=True, w_split=False):
+    """The split arm's own claim, fp32 round-off of the UNSPLIT fp32 operands, as a budget: (ref, budget) against the fp64
+    product of the fp32 x [M, K] and w [N, K], with the representation error of each split input (split_repr per element)
+    carried through the product: sum_k |dx_k| |w_k| + |x_k| |dw_k| + |dx_k| |dw_k|.  An unsplit input is taken as given."""
+    x64, w64 = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    lin, s = gemm_reference(x64, w64, bias)
+    dx = split_repr(x64) if x_split else np.zeros_like(x64)
+    dw = split_repr(w64) if w_split else np.zeros_like(w64)
+    din = dx @ np.abs(w64).T + np.abs(x64) @ dw.T + dx @ dw.T
+    return gemm_split_budget(lin, s, epi, out_split, resid0, din)
+
+
+def layernorm_split_budget(x, g, b, eps=1e-5):
+    """(ref, budget) of mcm_op_layernorm_split (ln_row_store<X2>): the fp32 LayerNorm value, stored as a split pair."""
+    ref, bud = layernorm_budget(x, g, b, "fp32", eps)
+    return ref, bud + split_repr(np.abs(ref) + bud)
+
+
+P_SCALE_LOG2 = 12   # the split attention kernels split P after a scale of 2^12 (attention.hip: msc = m * SC - 12)
+
+
+def attention_split_rows(qh, ql, kh, kl, vh, vl, scale=0.125):
+    """Terms of split attention (attn_tr_kernel<X2>, attn_long_kernel<X2>) for the query rows of qh / ql against all keys,
+    from the hi and lo halves [*, 64] of q, k, v.  The reference is fp64 softmax attention on the merged operands hi + lo.
+    Returns (ref, bud, dev, pv, smax), bud before the output is stored.
+      S = K_lo Q_hi + K_hi Q_lo + K_hi Q_hi, one fp32 chain of 3 x 64 products; the dropped Q_lo K_lo joins the logit
+        perturbation as scale |Q_lo| |K_lo|^T;
+      P = exp2(s SC - m SC + 12), 2^12 times the unnormalised softmax, split: relative U_SPLIT and the subnormal floor 2^-25
+        of the scaled value, i.e. 2^-37 of P.  There is no L 2^-25 max|v| term of the fp16 arm here: the scale removes it;
+      O = V_lo P_hi + V_hi P_lo + V_hi P_hi in one fp32 chain; the dropped P_lo V_lo (|P_lo| <= 2^-11 P + the floor) is a
+        term of its own; the row sum runs over P_lo and P_hi (the all-ones MFMA: two passes per 32-key step)."""
+    qh, ql, kh, kl, vh, vl = (np.asarray(a, np.float64) for a in (qh, ql, kh, kl, vh, vl))
+    q, k, v = qh + ql, kh + kl, vh + vl
+    L = k.shape[0]
+    s = scale * (q @ k.T)
+    sa = scale * ((np.abs(qh) + np.abs(ql)) @ (np.abs(kh) + np.abs(kl)).T)
+    m = s.max(axis=1, keepdims=True)
+    e = np.exp(s - m)
+    p = e / e.sum(axis=1, keepdims=True)
+    ref = p @ v
+    va = np.abs(vh) + np.abs(vl)
+    pv = p @ va
+    dev = np.einsum("qj,qjd->qd", p, np.abs(v[None, :, :] - ref[:, None, :]))
+    ds = (C_ACC * U32 * sa + U32 * (np.abs(s) + np.abs(m)) * 2.0 + C_EXP * U32
+          + scale * (np.abs(ql) @ np.abs(kl).T))                   # the dropped Q_lo K_lo
+    dsmax = ds.max(axis=1, keepdims=True)
+    p_floor = 2.0 ** (-25 - P_SCALE_LOG2)                          # per key, in units of the row's largest P (1)
+    bud = (2.0 * U_SPLIT * pv + 2.0 * L * p_floor * va.max()       # P's split, in O and in the row sum
+           + dsmax * dev                                           # logit / exp error, carried through the softmax
+           + C_ACC * U32 * pv                                      # fp32 accumulation of the three P.V passes
+           + 2.0 ** -11 * (p @ np.abs(vl)) + L * p_floor * np.abs(vl).max()   # the dropped P_lo V_lo
+           + (2 * math.ceil(L / 16) + 4) * U32 * np.abs(ref)      # the row sum over P_lo and P_hi
+           + 2.0 * U32 * np.abs(ref))                              # 1 / rowsum and the final product
+    return ref, bud, dev, pv, np.abs(s).max(axis=1, keepdims=True)
+
+
+def attention_split_budget(qh, ql, kh, kl, vh, vl, scale=0.125, row_block=128):
+    """(ref, budget) of one (sequence, head) of mcm_op_attention_split up to 288 keys: attention_split_rows plus the split
+    of the stored output (split_repr).  The streaming form: online_softmax_budget.online_attention_split_budget."""
+    refs, buds = [], []
+    for r0 in range(0, np.shape(qh)[0], row_block):
+        rb = slice(r0, r0 + row_block)
+        ref, bud, _, _, _ = attention_split_rows(qh[rb], ql[rb], kh, kl, vh, vl, scale)
+        refs.append(ref)
+        buds.append(bud + split_repr(np.abs(ref) + bud))
+    return np.concatenate(refs), np.concatenate(buds)
+
+
+def head_parts(img, L, heads, n, h):
+    """(qh, ql, kh, kl, vh, vl), each [L, 64] float64, of (sequence n, head h) of a split qkv image [nseq L, 6 heads 64]."""
+    hi, lo = image_parts(np.asarray(img)[n * L:(n + 1) * L])
+    D = heads * 64
+    return tuple(a[:, o + h * 64:o + (h + 1) * 64] for o in (0, D, 2 * D) for a in (hi, lo))
+
+
+def coherent_small_p_qkv(L, heads, nseq=1):
+    """The input on which P split WITHOUT the 2^12 scale breaks the split attention budget.  In every (sequence, head) key 0
+    dominates every query: raw logits q.k = +2t for key 0 and -2t for the L - 1 others (t ~ 25: after the 0.125 scale a gap
+    of 12.5, P ~ 2^-18 against key 0).  All those P are equal, so their rounding errors add up instead of cancelling, and t
+    is chosen (on a grid of 1/64, exact in fp16) so that the unscaled P's remainder after hi falls halfway between two points
+    of fp16's subnormal grid: each lo then misses by nearly 2^-25, the largest error there is.  V is 0 for key 0 and 1 for
+    the others (one sign).  Returns the fp32 qkv [nseq L, 3 heads 64]."""
+    D = heads * 64
+    SC = np.float32(0.125 * 1.4426950408889634)
+    best = None
+    for i in range(128):
+        t = 24.0 + i / 64.0
+        msc = np.float32(np.float64(2.0 * t) * np.float64(SC))             # the kernel's m * SC, unscaled
+        arg = np.float32(np.float64(-2.0 * t) * np.float64(SC) - np.float64(msc))   # fmaf(s, SC, -msc)
+        c = np.float32(np.exp2(np.float64(arg)))
+        r = (np.float64(c) - np.float64(np.float16(c))) / 2.0 ** -24
+        miss = abs(r - np.floor(r) - 0.5)
+        if best is None or miss < best[0]:
+            best = (miss, t)
+    t = best[1]
+    qkv = np.zeros((nseq * L, 3 * D), np.float32)
+    for h in range(heads):
+        qkv[:, h * 64] = 4.0
+        qkv[:, D + h * 64] = -0.5 * t
+        qkv[:, 2 * D + h * 64:2 * D + (h + 1) * 64] = 1.0
+        for n in range(nseq):
+            qkv[n * L, D + h * 64] = 0.5 * t
+            qkv[n * L, 2 * D + h * 64:2 * D + (h + 1) * 64] = 0.0
+    return qkv
 
 
 def worst(got, ref, bud):

@@ -78,6 +78,22 @@ def online_attention_budget(q, k, v, out: str, scale=0.125, online=True):
     return np.concatenate(refs), np.concatenate(buds)
 
 
+def online_attention_split_budget(qh, ql, kh, kl, vh, vl, scale=0.125):
+    """(ref, budget) of one (sequence, head) of the streaming split kernel (attn_long_kernel<X2>): the split terms of
+    error_budget.attention_split_rows, the rescale terms above, and the split of the stored output (error_budget.split_repr).
+    P is split against the running max after the same 2^12 scale; relative to its final weight each P's subnormal floor is
+    at most the whole-row model's (the running max is never above the final one)."""
+    L = np.shape(kh)[0]
+    refs, buds = [], []
+    for r0 in range(0, np.shape(qh)[0], ROW_BLOCK):
+        rb = slice(r0, r0 + ROW_BLOCK)
+        ref, bud, dev, pv, smax = eb.attention_split_rows(qh[rb], ql[rb], kh, kl, vh, vl, scale)
+        bud = bud + online_terms(L, dev, pv, ref, smax)
+        refs.append(ref)
+        buds.append(bud + eb.split_repr(np.abs(ref) + bud))
+    return np.concatenate(refs), np.concatenate(buds)
+
+
 def online_attention_qkv_budget(qkv, nseq, L, heads, out, pairs=None):
     """online_attention_budget over the (sequence, head) pairs of a [nseq * L, 3 * heads * 64] qkv (all pairs by default).
     Returns {(n, h): (ref [L, 64], budget [L, 64])}."""

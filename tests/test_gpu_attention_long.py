@@ -151,21 +151,8 @@ def test_long_attention_cls_only_rows(harness_net, prec):
     _budget_check("attention-long-cls", prec, qkv, full, nseq, L, heads, rows=slice(0, 1))
 
 
-def _split_image(x):
-    """fp32 [M, K] -> the split image [M, 2K] fp16: per 64 columns hi[64] then lo[64]."""
-    M, K = x.shape
-    hi = x.astype(np.float16)
-    lo = (x - hi.astype(np.float32)).astype(np.float16)
-    out = np.empty((M, K // 64, 2, 64), np.float16)
-    out[:, :, 0, :] = hi.reshape(M, K // 64, 64)
-    out[:, :, 1, :] = lo.reshape(M, K // 64, 64)
-    return out.reshape(M, 2 * K)
-
-
-def _merge_image(y):
-    M, N2 = y.shape
-    v = y.reshape(M, N2 // 128, 2, 64).astype(np.float64)
-    return (v[:, :, 0, :] + v[:, :, 1, :]).reshape(M, N2 // 2)
+_split_image = eb.split_image
+_merge_image = eb.merge_image
 
 
 def _attention_f64(qkv, nseq, L, heads):

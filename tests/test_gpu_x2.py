@@ -8,6 +8,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import error_budget as eb
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -25,22 +27,8 @@ def _dev(a, dtype=None):
     return t.to(dtype) if dtype is not None else t
 
 
-def split_image(x: np.ndarray) -> np.ndarray:
-    """fp32 [M, K] (K % 64 == 0) -> the split image [M, 2K] as float16: per 64 columns hi[64] then lo[64]."""
-    M, K = x.shape
-    hi = x.astype(np.float16)
-    lo = (x - hi.astype(np.float32)).astype(np.float16)
-    out = np.empty((M, K // 64, 2, 64), np.float16)
-    out[:, :, 0, :] = hi.reshape(M, K // 64, 64)
-    out[:, :, 1, :] = lo.reshape(M, K // 64, 64)
-    return out.reshape(M, 2 * K)
-
-
-def merge_image(y: np.ndarray) -> np.ndarray:
-    """split image [M, 2N] float16 -> fp32 [M, N] = hi + lo (exact in fp64, returned as float64)."""
-    M, N2 = y.shape
-    v = y.reshape(M, N2 // 128, 2, 64).astype(np.float64)
-    return (v[:, :, 0, :] + v[:, :, 1, :]).reshape(M, N2 // 2)
+split_image = eb.split_image   # fp32 [M, K] -> split image [M, 2K] fp16: per 64 columns hi[64] then lo[64]
+merge_image = eb.merge_image   # split image -> hi + lo (exact, float64)
 
 
 @pytest.fixture(scope="module")
