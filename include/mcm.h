@@ -442,6 +442,27 @@ int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, voi
  * direction. */
 int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                                  int32_t heads, int32_t qrows, int32_t reverse, void* stream);
+/* The front of the vision tower as mcm_encode_image* run it (the same function, the handle's own weights and workspace), stopped
+ * at `stage`: 0 = behind the patch-embedding GEMM, 1 = behind the fused CLS row + pre_layrnorm + layer 0 layer_norm1 pass.  The
+ * fp32 residual rows [B * tokens, v_width] are copied to resid_out_dev (at stage 0 the CLS rows are whatever the workspace held);
+ * at stage 1 the first QKV operand rows are copied to ln_out_dev: [B * tokens, v_width] in the operand dtype, or the split image
+ * [B * tokens, 2 v_width] fp16 with x2.  pixel_format: MCM_PIXELS_*; x2: the split-activation arm.  poison != 0: the patch
+ * matrix and the residual rows are filled with 0xFF bytes first (NaN in every operand format).  The route (pixel-gathering GEMM
+ * or patchify + GEMM) is the product's own choice, mcm_debug_patch_fold included. */
+int mcm_debug_vision_front(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t x2, int32_t B, int32_t stage,
+                           int32_t poison, float* resid_out_dev, void* ln_out_dev, void* stream);
+/* The pooling kernel of both towers on the caller's buffers: row i of out [n, P] = normalise?(LayerNorm(x[row]) proj^T) with
+ * row = row_idx_host[i], or i * row_stride when row_idx_host is NULL; x [x_rows, D] fp32, proj [P, D] fp32.  The indices are
+ * host memory and are checked against x_rows.  MCM_EINVAL for D > 1024, D % 4 != 0, P > 1024 or a row outside x.
+ * Synchronises the stream. */
+int mcm_debug_op_pool_project(mcm_handle* h, const float* x_dev, int64_t x_rows, const int32_t* row_idx_host, int32_t row_stride,
+                              int32_t n, int32_t D, const float* gamma_dev, const float* beta_dev, float eps,
+                              const float* proj_dev, int32_t P, float* out_dev, int32_t normalize, void* stream);
+/* The text embedding kernel on the caller's buffers: x [K * S, D] = tok[ids[k * S + s]] + pos[s]; tok [vocab, D], pos with at
+ * least S rows.  The ids are host memory and are checked against vocab.  MCM_EINVAL for D % 4 != 0 or an id outside the table.
+ * Synchronises the stream. */
+int mcm_debug_op_text_embed(mcm_handle* h, const int32_t* ids_host, int32_t vocab, const float* tok_dev, const float* pos_dev,
+                            float* x_dev, int32_t K, int32_t S, int32_t D, void* stream);
 /* A/B and ablation bits of the GEMM kernels (gemm.hip, GemmArgs::dbg; 0 = shipped behaviour). */
 int mcm_debug_gemm_dbg(int32_t bits);
 /* A/B: run the QKV projection + attention of every layer per chunk of the batch (n chunks; 1 = shipped). */

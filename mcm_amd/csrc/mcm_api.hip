@@ -882,16 +882,10 @@ namespace {
 const float kClipMean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
 const float kClipStd[3] = {0.26862954f, 0.26130258f, 0.27577711f};
 
-// x2: the split-activation arm (include/mcm.h mcm_score_x2) — same weights, same workspace, B <= h->x2_batch
-int encode_image_impl(mcm_handle* h, const void* pixels_dev, bool u8, int32_t B, float* out_dev,
-                      void* stream, bool normalize = true, bool x2 = false) {
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (!pixels_dev || !out_dev) return fail(h, MCM_EINVAL, "null pointer");
-  if (x2 && h->x2_batch <= 0) return fail(h, MCM_EINVAL, "the split-activation arm needs an fp16 handle created with a split-activation workspace (cfg.x2_max_batch >= 0)");
-  if (B <= 0 || B > (x2 ? h->x2_batch : h->cfg.max_batch))
-    return fail(h, MCM_ERANGE, x2 ? "batch exceeds mcm_x2_max_batch" : "batch exceeds cfg.max_batch");
-  hipStream_t s = (hipStream_t)stream;
+// The front of the vision tower, up to the first encoder layer's QKV operand: pixels -> patch GEMM (+ position rows, written
+// around the CLS slots of h->x) -> pad rows zeroed -> CLS row, pre_layrnorm (h->x, fp32) and layer 0's layer_norm1 (h->ln) in
+// one pass.  stage_last: 1 = all of it (encode_image_impl); 0 = stop behind the patch GEMM (harness: mcm_debug_vision_front).
+int vision_front(mcm_handle* h, hipStream_t s, const void* pixels_dev, bool u8, int32_t B, bool x2, int stage_last = 1) {
   const mcm_config& c = h->cfg;
   const int D = c.v_width;
 
@@ -916,6 +910,7 @@ int encode_image_impl(mcm_handle* h, const void* pixels_dev, bool u8, int32_t B,
   a.M = B * h->np; a.N = D; a.K = h->kpad; a.ldx = h->kpad; a.ldo = D; a.np = h->np; a.ksplit = h->vis.split ? 1 : 0;
   a.xsplit = x2 ? 1 : 0;
   HIP_TRY(h, gemm(h, s, c.precision, EPI_PATCH, a));
+  if (stage_last < 1) return MCM_OK;
   {  // Pad rows.  gemm() runs the dense activation GEMMs on whole 256-row tiles; the rows between B * ntok and the next
      // multiple of 256 are computed and never read.  The buffers they live in are shared with the fp32 text tower, so
      // what they hold is arbitrary (fp32 bit patterns read as fp16 decode to inf / NaN, which would trip the saturation
@@ -940,6 +935,29 @@ int encode_image_impl(mcm_handle* h, const void* pixels_dev, bool u8, int32_t B,
                                     h->sat_on ? h->sat_dev : nullptr,
                                     W(h, "vision_model.embeddings.class_embedding"), a.pos, h->ntok, x2));
   }
+  return MCM_OK;
+}
+
+// the argument checks of every image entry point
+int check_image_call(mcm_handle* h, const void* pixels_dev, const void* out_dev, int32_t B, bool x2) {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!pixels_dev || !out_dev) return fail(h, MCM_EINVAL, "null pointer");
+  if (x2 && h->x2_batch <= 0) return fail(h, MCM_EINVAL, "the split-activation arm needs an fp16 handle created with a split-activation workspace (cfg.x2_max_batch >= 0)");
+  if (B <= 0 || B > (x2 ? h->x2_batch : h->cfg.max_batch))
+    return fail(h, MCM_ERANGE, x2 ? "batch exceeds mcm_x2_max_batch" : "batch exceeds cfg.max_batch");
+  return MCM_OK;
+}
+
+// x2: the split-activation arm (include/mcm.h mcm_score_x2) — same weights, same workspace, B <= h->x2_batch
+int encode_image_impl(mcm_handle* h, const void* pixels_dev, bool u8, int32_t B, float* out_dev,
+                      void* stream, bool normalize = true, bool x2 = false) {
+  int rc = check_image_call(h, pixels_dev, out_dev, B, x2);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const mcm_config& c = h->cfg;
+  const int D = c.v_width;
+  if ((rc = vision_front(h, s, pixels_dev, u8, B, x2))) return rc;
   if ((rc = run_layers(h, s, h->vis, B, h->ntok, false, true, true, true, x2))) return rc;
   {
     Scope sc(h, s, MCM_KC_POOL_PROJECT, 2.0 * B * D * c.proj_dim);
@@ -1432,6 +1450,89 @@ int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_d
   if (!h) return MCM_EINVAL;
   HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, false, qrows, (hipStream_t)stream,
                               reverse != 0, 0, true));
+  return MCM_OK;
+}
+
+// The front of encode_image_impl (vision_front: the same calls on the handle's own weights and workspace), stopped at `stage`
+// (0: behind the patch GEMM, 1: behind launch_layernorm_pre), with the fp32 residual rows [B ntok, D] copied to resid_out_dev
+// and, at stage 1, the operand rows h->ln (16-bit / fp32 [B ntok, D], or the split image [B ntok, 2 D]) to ln_out_dev.
+// poison: the patch matrix and the residual rows of this batch are filled with 0xFF bytes first (NaN as bf16, fp16 and fp32):
+// a pad column that is not written as zero, or a CLS row read instead of synthesised, shows as a NaN.
+int mcm_debug_vision_front(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t x2, int32_t B, int32_t stage,
+                           int32_t poison, float* resid_out_dev, void* ln_out_dev, void* stream) {
+  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC) return fail(h, MCM_EINVAL, "unknown pixel_format");
+  int rc = check_image_call(h, pixels_dev, resid_out_dev, B, x2 != 0);
+  if (rc) return rc;
+  if (stage < 0 || stage > 1 || (stage == 1 && !ln_out_dev)) return fail(h, MCM_EINVAL, "stage 0 or 1; stage 1 needs ln_out_dev");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t es = (size_t)prec_esize(h->cfg.precision) * (x2 ? 2 : 1), rows = (size_t)B * h->ntok, D = (size_t)h->cfg.v_width;
+  if (poison) {
+    HIP_TRY(h, hipMemsetAsync(h->patches, 0xFF, (size_t)B * h->np * h->kpad * es, s));
+    HIP_TRY(h, hipMemsetAsync(h->x, 0xFF, rows * D * sizeof(float), s));
+  }
+  if ((rc = vision_front(h, s, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, x2 != 0, stage))) return rc;
+  HIP_TRY(h, hipMemcpyAsync(resid_out_dev, h->x, rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (stage == 1) HIP_TRY(h, hipMemcpyAsync(ln_out_dev, h->ln, rows * D * es, hipMemcpyDeviceToDevice, s));
+  return MCM_OK;
+}
+
+// launch_pool_project as the towers call it: the pooled rows of x [x_rows, D] by index (row_idx_host, n entries) or by stride
+// (row_idx_host NULL).  The indices come from the host and are checked against x_rows here (the towers compute theirs on the
+// host as well); the call synchronises the stream.
+int mcm_debug_op_pool_project(mcm_handle* h, const float* x_dev, int64_t x_rows, const int32_t* row_idx_host, int32_t row_stride,
+                              int32_t n, int32_t D, const float* gamma_dev, const float* beta_dev, float eps,
+                              const float* proj_dev, int32_t P, float* out_dev, int32_t normalize, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!x_dev || !gamma_dev || !beta_dev || !proj_dev || !out_dev || n <= 0 || D <= 0 || P <= 0 || x_rows <= 0 || row_stride < 0)
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (row_idx_host) {
+    for (int32_t i = 0; i < n; ++i)
+      if (row_idx_host[i] < 0 || row_idx_host[i] >= x_rows) return fail(h, MCM_EINVAL, "row index outside x");
+  } else if ((int64_t)(n - 1) * row_stride >= x_rows) {
+    return fail(h, MCM_EINVAL, "strided rows outside x");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* idx_dev = nullptr;
+  if (row_idx_host) {
+    HIP_TRY(h, hipMalloc((void**)&idx_dev, (size_t)n * sizeof(int32_t)));
+    hipError_t e = hipMemcpy(idx_dev, row_idx_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(idx_dev);
+      HIP_TRY(h, e);
+    }
+  }
+  hipError_t e = launch_pool_project(x_dev, idx_dev, row_stride, n, D, gamma_dev, beta_dev, eps, proj_dev, P, out_dev, s,
+                                     normalize != 0);
+  const bool refused = e == hipErrorInvalidValue;  // the launcher's own shape guard: nothing was launched
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (idx_dev) (void)hipFree(idx_dev);
+  if (refused) return fail(h, MCM_EINVAL, "launch_pool_project refused the shape (D <= 1024, D % 4 == 0, P <= 1024)");
+  HIP_TRY(h, e);
+  return MCM_OK;
+}
+
+// launch_text_embed: x[k S + s] = tok[ids[k S + s]] + pos[s]; tok [vocab, D], pos [>= S rows, D].  The ids come from the host
+// and are checked against vocab here, as mcm_encode_text_ex checks its own; the call synchronises the stream.
+int mcm_debug_op_text_embed(mcm_handle* h, const int32_t* ids_host, int32_t vocab, const float* tok_dev, const float* pos_dev,
+                            float* x_dev, int32_t K, int32_t S, int32_t D, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!ids_host || !tok_dev || !pos_dev || !x_dev || K <= 0 || S <= 0 || D <= 0 || vocab <= 0) return fail(h, MCM_EINVAL, "bad argument");
+  const size_t nid = (size_t)K * S;
+  for (size_t i = 0; i < nid; ++i)
+    if (ids_host[i] < 0 || ids_host[i] >= vocab) return fail(h, MCM_EINVAL, "token id out of range");
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* ids_dev = nullptr;
+  HIP_TRY(h, hipMalloc((void**)&ids_dev, nid * sizeof(int32_t)));
+  hipError_t e = hipMemcpy(ids_dev, ids_host, nid * sizeof(int32_t), hipMemcpyHostToDevice);
+  bool refused = false;
+  if (e == hipSuccess) {
+    e = launch_text_embed(ids_dev, tok_dev, pos_dev, x_dev, K, S, D, s);
+    refused = e == hipErrorInvalidValue;  // the launcher's own shape guard: nothing was launched
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ids_dev);
+  if (refused) return fail(h, MCM_EINVAL, "launch_text_embed refused the shape (D % 4 == 0)");
+  HIP_TRY(h, e);
   return MCM_OK;
 }
 

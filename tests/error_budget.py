@@ -111,15 +111,17 @@ def layernorm_reference(x, g, b, eps=1e-5):
     return c / np.sqrt(var + eps) * np.asarray(g, np.float64) + np.asarray(b, np.float64)
 
 
-def layernorm_budget(x, g, b, out: str, eps=1e-5):
-    """(ref, budget) of the LayerNorm kernel (ln_row.hpp: fp32 two-pass statistics, one wave per row)."""
+def layernorm_budget(x, g, b, out: str, eps=1e-5, depth=None):
+    """(ref, budget) of the LayerNorm kernel (ln_row.hpp: fp32 two-pass statistics, one wave per row).
+    depth: the depth of the summation tree when it is not the row kernel's (pool_project_budget)."""
     x64 = np.asarray(x, np.float64)
     D = x64.shape[1]
     ref = layernorm_reference(x, g, b, eps)
     mu = x64.mean(axis=1, keepdims=True)
     rstd = 1.0 / np.sqrt(((x64 - mu) ** 2).mean(axis=1, keepdims=True) + eps)
     g64, b64 = np.abs(np.asarray(g, np.float64)), np.abs(np.asarray(b, np.float64))
-    depth = math.ceil(math.log2(D)) + 4
+    if depth is None:
+        depth = math.ceil(math.log2(D)) + 4
     # the fp32 row sum (ln_part_sum: <= 16 values per lane, then the 6-step wave_sum: a tree of depth <= log2(D) + 4) and
     # the division by D: the mean is off by this much, and every centred value with it (x - mean is exact-ish)
     dmean = depth * U32 * np.abs(x64).mean(axis=1, keepdims=True) + U32 * np.abs(mu)
@@ -437,6 +439,162 @@ def coherent_small_p_qkv(L, heads, nseq=1):
             qkv[n * L, D + h * 64] = 0.5 * t
             qkv[n * L, 2 * D + h * 64:2 * D + (h + 1) * 64] = 0.0
     return qkv
+
+
+# ---- the two ends of the towers: pixels / token ids -> residual stream, residual stream -> unit vectors -----------------
+# preprocess constants of the reference (utils/train_eval_util.py:27-28), as fp32 (mcm_api.hip kClipMean / kClipStd)
+CLIP_MEAN = np.array([0.48145466, 0.4578275, 0.40821073], np.float32)
+CLIP_STD = np.array([0.26862954, 0.26130258, 0.27577711], np.float32)
+
+
+def patchify_reference(px, P: int, kpad: int) -> np.ndarray:
+    """fp32 NCHW pixels [B, 3, S, S] -> the patch matrix [B * np, kpad] (values unchanged): row b * np + gy * g + gx, column
+    k = (c * P + py) * P + px, the [D, 3, P, P] weight's own flattening (embed.hip patchify_kernel); columns from 3 P P on
+    are zero (L/14: 588 -> 640)."""
+    px = np.asarray(px, np.float32)
+    B, C, S, _ = px.shape
+    g = S // P
+    m = px.reshape(B, C, g, P, g, P).transpose(0, 2, 4, 1, 3, 5).reshape(B * g * g, C * P * P)
+    out = np.zeros((B * g * g, kpad), np.float32)
+    out[:, :C * P * P] = m
+    return out
+
+
+def u8_normalise(u8) -> np.ndarray:
+    """uint8 NHWC [B, S, S, 3] -> fp32 NCHW: ((float32(u8) / 255f) - mean) / std, each operation rounded to fp32 in that
+    order (patchify_u8_kernel; torchvision's ToTensor then Normalize).  HIP's fp32 division is correctly rounded, so is
+    numpy's: the kernel's operand is expected to equal this bit for bit."""
+    t = np.asarray(u8, np.uint8).astype(np.float32) / np.float32(255.0)
+    v = (t - CLIP_MEAN) / CLIP_STD
+    return np.ascontiguousarray(v.transpose(0, 3, 1, 2), dtype=np.float32)
+
+
+def operand_values(v, mode: str, x2: bool = False) -> np.ndarray:
+    """The values an fp32 activation is multiplied as (float64): itself in fp32 mode, rounded to nearest even in the 16-bit
+    modes (fp16: f16_sat), hi + lo of split2_f16 with x2."""
+    v = np.asarray(v, np.float32)
+    if x2:
+        hi, lo = split2_f16(v)
+        return hi.astype(np.float64) + lo.astype(np.float64)
+    if mode == "fp32":
+        return v.astype(np.float64)
+    if mode == "fp16":
+        return f16_sat(v).astype(np.float64)
+    return round_to(v, mode).astype(np.float64)
+
+
+def weight_values(w, mode: str, split: bool) -> np.ndarray:
+    """The values a handle multiplies for the fp32 master weight w (float64): w in fp32 mode, round(w) as one 16-bit operand,
+    or hi + lo with hi = round(w), lo = round(w - hi) when the handle holds split weights (embed.hip cvt_weight_split_kernel)."""
+    w = np.asarray(w, np.float32)
+    if mode == "fp32":
+        return w.astype(np.float64)
+    if not split:
+        return round_to(w, mode).astype(np.float64)
+    if mode == "fp16":
+        hi, lo = split2_f16(w)
+        return hi.astype(np.float64) + lo.astype(np.float64)
+    hi = round_to(w, mode)
+    return hi.astype(np.float64) + round_to(w - hi, mode).astype(np.float64)
+
+
+def patch_embed_budget(patches, w, pos, n_patches: int, rows=None):
+    """(ref, budget) of the EPI_PATCH epilogue (gemm.hip wave_epilogue / the LDS-staged epilogue of gemm_p256_kernel, plain and
+    pixel-gathering): out[b (np + 1) + 1 + p] = pos[1 + p] + patches[b np + p] . w^T in fp32.  patches [M, K] and w [D, K] are
+    the operands as multiplied (operand_values / weight_values, the K padding included), pos [np + 1, D] fp32; rows: the
+    patch-matrix rows given (all M by default).  Returns arrays over those rows, in patch-matrix order.
+    The terms are gemm_budget's residual rule with the position row in the residual's place: the fp32 add of the position
+    row (<= 1/2 ulp, and the result may sit in the next binade: 1 ulp), the fp32 MFMA chain over the K-steps (2 K or 4 K
+    products with a split operand: C_ACC covers them, test_c_acc_covers_split_chains), and the rounding of the chain's value
+    (the epilogue's acc + 0 bias is exact)."""
+    rows = np.arange(np.shape(patches)[0]) if rows is None else np.asarray(rows)
+    lin, s = gemm_reference(patches, w, np.zeros(np.shape(w)[0]))
+    return gemm_budget(lin, s, "fp32", 2, np.asarray(pos, np.float64)[1 + rows % n_patches])
+
+
+def token_rows(B: int, n_patches: int, rows=None) -> np.ndarray:
+    """Residual-stream row of each patch-matrix row: b np + p -> b (np + 1) + 1 + p."""
+    rows = np.arange(B * n_patches) if rows is None else np.asarray(rows)
+    return rows // n_patches * (n_patches + 1) + 1 + rows % n_patches
+
+
+def cls_row(cls, pos) -> np.ndarray:
+    """The CLS row layernorm_pre_kernel synthesises in registers: float32(class_embedding + position_embedding[0]), one
+    correctly rounded add per element: exact, no budget."""
+    return np.asarray(cls, np.float32) + np.asarray(pos, np.float32)[0]
+
+
+def pre_ln_budgets(x0, x1, g0, b0, g1, b1, mode: str, x2: bool = False, eps=1e-5):
+    """The fused pass of layernorm_pre_kernel as two applications of layernorm_budget.
+      x0: the kernel's own fp32 input rows (the patch GEMM's rows, the CLS rows replaced by cls_row); pre_layrnorm of them is
+          written back in fp32: budget 1, output format "fp32";
+      x1: the fp32 rows the kernel wrote back.  It normalises exactly those values again (still in registers: ln_row_store
+          <MCM_PREC_F32> stores v unchanged), into the mode's operand format: budget 2, or the split budget with x2.
+    Both passes are ln_row_apply<0> (ln_row.hpp), the function layernorm_kernel calls: ln_part_sum adds (x + y) + (z + w) of up
+    to four float4 per lane (depth <= 2 + 4), wave_sum is a 6-step butterfly: at most 12 <= ceil(log2 D) + 4 for every D from
+    128 on, and D = 64 has one float4 in 16 lanes (depth 2 + 6 = 8 <= 10): layernorm_budget's depth term describes it.
+    Returns ((ref_pre, bud_pre), (ref_ln1, bud_ln1))."""
+    first = layernorm_budget(x0, g0, b0, "fp32", eps)
+    second = layernorm_split_budget(x1, g1, b1, eps) if x2 else layernorm_budget(x1, g1, b1, mode, eps)
+    return first, second
+
+
+def eos_rows(ids) -> np.ndarray:
+    """Pooled row of every prompt of ids [K, S]: k S + the FIRST position of the largest id (HF modeling_clip.py:561-581;
+    mcm_encode_text_ex)."""
+    ids = np.asarray(ids)
+    return np.arange(ids.shape[0]) * ids.shape[1] + ids.argmax(axis=1)
+
+
+POOL_WAVES = 16   # embed.hip NWP: waves of a pool_project workgroup
+
+
+def l2_normalise_budget(o, do, n_add: int):
+    """(ref, budget) of out = o / ||o||_2 per row, o known to within do per element, the sum of squares an fp32 sum of
+    positive terms with at most n_add additions on any path.
+      do / ||o||                      the element's own error, scaled;
+      |out| ||do||_2 / ||o||          the norm's error from the elements' errors: | ||o + e|| - ||o|| | <= ||e||_2;
+      |out| (n_add / 2 + 3) u32       the squares and their fp32 sum (relative (n_add + 1) u32 of the sum, half of it after the
+                                      square root), sqrtf, 1 / . (both correctly rounded) and the product o * rn.
+    A row of norm 0 has no finite budget (the kernels return 0 * inf there, as the reference's x / x.norm() does)."""
+    o64, do = np.asarray(o, np.float64), np.asarray(do, np.float64)
+    nrm = np.sqrt((o64 * o64).sum(axis=1, keepdims=True))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ref = o64 / nrm
+        bud = do / nrm + np.abs(ref) * np.sqrt((do * do).sum(axis=1, keepdims=True)) / nrm \
+            + np.abs(ref) * (0.5 * n_add + 3.0) * U32
+    return ref, np.where(nrm > 0, bud + 0.5 * ulp(np.where(nrm > 0, ref, 0.0), "fp32"), np.inf)
+
+
+def pool_project_budget(x, g, b, proj, normalize: bool, eps=1e-5):
+    """(ref, budget) of pool_project_kernel (embed.hip) on the pooled fp32 rows x [n, D]; proj [P, D] fp32.
+      LayerNorm   one element per thread, wave_sum (6 steps), the 16 wave partials added one after another by every thread:
+                  a tree of depth 6 + 16 whatever D is (threads past D add exact zeros), against the row kernel's
+                  ceil(log2 D) + 4 -> layernorm_budget with that depth, fp32 output (y in LDS): dy;
+      projection  o_p = sum_d w_pd y_d, an fmaf chain of D / 64 terms per lane and the butterfly:
+                  do = sum_d |w| dy + C_ACC u32 sum_d |w| |y|.  C_ACC is the file's one accumulation constant, chosen on
+                  the CPU for fp32 dot products (test_c_acc_covers_cpu_dot_products); it is NOT a strict worst-case bound
+                  here once D > 640: a path then has up to 16 fmaf roundings and 6 butterfly adds, 22 > 16.  The kernel-order
+                  emulation stays below 0.14 of the whole budget at every D (test_pool_project_emulation_within_budget);
+      normalise   the squares of a wave's outputs (every 16th p) summed by its lane 0 one after another (ceil(P / 16) terms),
+                  then the 16 partials: l2_normalise_budget with n_add = ceil(P / 16) + 16."""
+    y, dy = layernorm_budget(x, g, b, "fp32", eps, depth=6 + POOL_WAVES)
+    w64 = np.asarray(proj, np.float64)
+    o = y @ w64.T
+    do = dy @ np.abs(w64).T + C_ACC * U32 * (np.abs(y) @ np.abs(w64).T)
+    if not normalize:
+        return o, do + 0.5 * ulp(o, "fp32")
+    return l2_normalise_budget(o, do, math.ceil(w64.shape[0] / POOL_WAVES) + POOL_WAVES)
+
+
+def bank_reduce_budget(feats, K: int, T: int):
+    """(ref, budget) of bank_reduce_kernel (embed.hip): feats [K T, P] fp32, class-major.  a = (sum_t f_t) / T with the sum
+    taken one term after another in fp32 (T - 1 roundings, each at most u32 of sum_t |f_t|) and one correctly rounded
+    division; then the normalise term: a lane sums the squares of its ceil(P / 64) elements, then the 6-step butterfly."""
+    f = np.asarray(feats, np.float64).reshape(K, T, -1)
+    a = f.mean(axis=1)
+    da = (T - 1) * U32 * np.abs(f).sum(axis=1) / T + U32 * np.abs(a)
+    return l2_normalise_budget(a, da, math.ceil(f.shape[2] / 64) + 6)
 
 
 def worst(got, ref, bud):

@@ -712,3 +712,304 @@ def test_sample_rows():
     assert r[0] == 0 and r[-1] == 76999 and 255 in r and 76744 in r
     assert all(b in r and b - 1 in r for b in range(64, 77000, 64))
     assert len(np.unique(r)) == len(r)
+
+
+# ---- the two ends of the towers (test_gpu_tower_ends_budget.py) ----------------------------------------------------------
+# Emulations of the EPI_PATCH GEMM behind each operand gather, of layernorm_pre_kernel, pool_project_kernel and
+# bank_reduce_kernel in fp32 and in kernel order, on the GPU tests' own input generators: inside their budgets; each planted
+# mistake outside.
+from tests import test_gpu_tower_ends_budget as ends  # noqa: E402  (its generators; nothing in it touches a GPU on import)
+
+
+def _butterfly(v):
+    """wave_sum over the last axis (64 lanes): v += shfl_xor(v, 32), 16, ... 1; every lane ends with the total."""
+    for o in (32, 16, 8, 4, 2, 1):
+        v = _f32(v + v[..., np.arange(64) ^ o])
+    return v
+
+
+def _seq_sum(parts):
+    """tot = 0; for i: tot += parts[..., i] in fp32."""
+    tot = np.zeros(parts.shape[:-1], F32)
+    for i in range(parts.shape[-1]):
+        tot = _f32(tot + parts[..., i])
+    return tot
+
+
+def _smooth_pos(ntok, D, seed):
+    """A position table whose neighbouring rows differ by about 1e-3 relative."""
+    base = (0.1 * np.random.default_rng(seed).standard_normal(D)).astype(F32)
+    base = np.where(np.abs(base) < 0.02, F32(0.05), base)
+    return _f32(base[None, :] * (1 + 1e-3 * np.arange(ntok))[:, None])
+
+
+def _patch_case(mode, x2, split, seed, u8=False):
+    """Two images of 2 x 2 patches of 14 pixels: L/14's K = 588 padded to 640 (16-bit modes) / 608 (fp32)."""
+    rng = np.random.default_rng(seed)
+    B, S, P, D = 2, 28, 14, 48
+    kreal = 3 * P * P
+    kalign = 32 if mode == "fp32" else 64
+    kpad = (kreal + kalign - 1) // kalign * kalign
+    if u8:
+        px = eb.u8_normalise(ends._u8(B, S, seed))
+    else:
+        px = ends._pixels(B, S, seed, device="cpu").numpy()
+    w = np.zeros((D, kpad), F32)
+    w[:, :kreal] = rng.standard_normal((D, kreal)) * kreal ** -0.5
+    if not split:
+        w = _f32(eb.weight_values(w, mode, False))
+    return px, w, _smooth_pos(5, D, seed), P, kpad
+
+
+def _patch_emulate(px, w, pos, P, kpad, mode, x2, split, mutation=None):
+    """patchify (operand rounding, zero pad) then the fp32 MFMA chain K-step after K-step (a split operand: one more stretch
+    of the same chain per half) and the epilogue's float32(acc + pos[1 + p])."""
+    pm = eb.patchify_reference(px, P, kpad)
+    n_patches = (px.shape[2] // P) ** 2
+    if mutation == "pad":       # the pad columns left as a poisoned workspace holds them
+        pm[:, 3 * P * P:] = np.nan
+    kstep = 32 if mode == "fp32" else 64
+    if x2:
+        hi, lo = eb.split2_f16(pm)
+        xs = [hi.astype(F32), lo.astype(F32)]
+    elif mode == "fp32":
+        xs = [pm]
+    elif mutation == "trunc":
+        xs = [_trunc16(pm, mode)]
+    else:
+        xs = [_f32(eb.operand_values(pm, mode))]
+    if split:
+        if mode == "fp16":
+            wh, wl = (a.astype(F32) for a in eb.split2_f16(w))
+        else:
+            wh = eb.round_to(w, mode)
+            wl = eb.round_to(w - wh, mode)
+        ws = [wh, wl]
+    else:
+        ws = [w]
+    xcat = np.concatenate([x for _ in ws for x in xs], axis=1)
+    wcat = np.concatenate([wv for wv in ws for _ in xs], axis=1)
+    with np.errstate(invalid="ignore"):
+        acc = _dot_seq(xcat, wcat, kstep)
+        rows = np.arange(pm.shape[0])
+        prow = rows % n_patches + (0 if mutation == "pos" else 1)
+        return _f32(acc + pos[prow])
+
+
+PATCH_FORMS = [("bf16", False, False), ("bf16", False, True), ("fp16", False, False), ("fp16", False, True),
+               ("fp16", True, False), ("fp16", True, True), ("fp32", False, False)]
+
+
+def _patch_ratio(mode, x2, split, mutation=None, u8=False, seed=3):
+    px, w, pos, P, kpad = _patch_case(mode, x2, split, seed, u8)
+    got = _patch_emulate(px, w, pos, P, kpad, mode, x2, split, mutation)
+    pm = eb.patchify_reference(px, P, kpad)
+    ref, bud = eb.patch_embed_budget(eb.operand_values(pm, mode, x2), eb.weight_values(w, mode, split), pos, 4)
+    assert np.isfinite(bud).all()
+    return eb.worst(got, ref, bud)[0]
+
+
+@pytest.mark.parametrize("mode,x2,split", PATCH_FORMS)
+def test_patch_embedding_emulation_within_budget(mode, x2, split):
+    for u8 in (False, True):
+        r = _patch_ratio(mode, x2, split, u8=u8)
+        assert r <= 1.0, (mode, x2, split, u8, r)
+
+
+@pytest.mark.parametrize("mutation", ["pos", "trunc", "pad"])
+def test_patch_embedding_mutations_break_the_budget(mutation):
+    """The position row p instead of 1 + p on a smooth table; pixels truncated instead of rounded to nearest even (the
+    16-bit single-operand modes: fp32 and the split gather have no rounding to get wrong); pad columns left as the poisoned
+    workspace holds them (NaN x 0).  A FINITE value in a pad column changes no output (the weight's pad columns are zero): that
+    is not a mistake an output can show, which is what the poison flag of mcm_debug_vision_front is for."""
+    forms = [f for f in PATCH_FORMS if mutation != "trunc" or (f[0] != "fp32" and not f[1])]
+    for mode, x2, split in forms:
+        r = _patch_ratio(mode, x2, split, mutation)
+        print(f"patch {mutation} {mode} x2={x2} wsplit={split}: budget ratio {r:.3g}")
+        assert r > 1.0, (mutation, mode, x2, split, r)
+
+
+def test_uint8_normalise_written_as_one_multiply_is_not_bit_equal():
+    """u8 * (1 / (255 std)) - mean / std in fp32 instead of ((u8 / 255) - mean) / std: an fp32 ulp or two away on most of the
+    768 (value, channel) pairs.  No budget of the patch GEMM can show an operand that is off by an fp32 ulp (its accumulation
+    term is 16 of them); the GPU test's bit-equality with eb.u8_normalise does."""
+    u8 = np.arange(256, dtype=np.uint8)[None, :, None, None] * np.ones((1, 1, 1, 3), np.uint8)
+    want = eb.u8_normalise(u8)
+    scale, shift = _f32(F32(1) / _f32(F32(255) * eb.CLIP_STD)), _f32(eb.CLIP_MEAN / eb.CLIP_STD)
+    got = _f32(_f32(u8.astype(F32) * scale) - shift).transpose(0, 3, 1, 2)
+    differ = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+    print(f"uint8 normalise as one multiply: {differ} of 768 pairs differ")
+    assert differ > 100
+    fused = _f32(u8.astype(np.float64) * scale - shift).transpose(0, 3, 1, 2)    # ... or contracted to one fma
+    assert int((fused.view(np.uint32) != want.view(np.uint32)).sum()) > 100
+
+
+@pytest.mark.parametrize("mode,x2", [("bf16", False), ("fp16", False), ("fp16", True), ("fp32", False)])
+def test_fused_pre_layernorm_emulation_within_budget_and_wrong_cls_row_breaks_it(mode, x2):
+    """layernorm_pre_kernel: the CLS row float32(cls + pos[0]), ln_row_apply twice.  Planted: the CLS row built from pos[1]
+    (smooth table), and layer_norm1 applied to the kernel's INPUT instead of to the rows it wrote back."""
+    D, B, ntok = 128, 3, 5
+    rng = np.random.default_rng(D)
+    pos = _smooth_pos(ntok, D, 1)
+    cls = (0.5 * rng.standard_normal(D)).astype(F32)
+    g0, b0 = (1 + 0.1 * rng.standard_normal(D)).astype(F32), (0.05 * rng.standard_normal(D)).astype(F32)
+    g1, b1 = (1 + 0.1 * rng.standard_normal(D)).astype(F32), (0.05 * rng.standard_normal(D)).astype(F32)
+    x = (rng.standard_normal((B * ntok, D)) * 0.8).astype(F32)
+    x[::ntok] = np.nan                                   # what the CLS slots hold does not matter
+
+    def run(cls_pos_row=0, ln1_of_input=False):
+        x0 = x.copy()
+        x0[::ntok] = _f32(cls + pos[cls_pos_row])
+        x1 = _ln_emulate(x0, g0, b0, "fp32")
+        y = _ln_emulate(x0 if ln1_of_input else x1, g1, b1, "fp32")
+        if x2:
+            return x1, eb.merge_image(eb.split_image(y))
+        return x1, y if mode == "fp32" else _f32(eb.operand_values(y, mode))
+
+    x0 = x.copy()
+    x0[::ntok] = eb.cls_row(cls, pos)
+    x1, y = run()
+    (r0, bud0), (r1, bud1) = eb.pre_ln_budgets(x0, x1, g0, b0, g1, b1, mode, x2)
+    assert np.isfinite(bud0).all() and np.isfinite(bud1).all()
+    assert eb.worst(x1, r0, bud0)[0] <= 1.0 and eb.worst(y, r1, bud1)[0] <= 1.0
+    x1b, _ = run(cls_pos_row=1)
+    r_cls = eb.worst(x1b, r0, bud0)[0]
+    _, yb = run(ln1_of_input=True)
+    r_in = eb.worst(yb, r1, bud1)[0]
+    print(f"pre-ln {mode} x2={x2}: CLS from pos[1] {r_cls:.3g}, layer_norm1 of the input {r_in:.3g}")
+    assert r_cls > 1.0 and r_in > 1.0
+
+
+def _pool_emulate(x, g, b, proj, normalize, mutation=None, eps=1e-5):
+    """pool_project_kernel in fp32 and in its order: thread t holds x[t]; wave_sum, 16 partials added in turn; centred
+    squares the same way; y = c * rstd * g + b; per output p the lanes' fmaf chains over d = lane * 4 + 256 i + j and the
+    butterfly; lane 0 of wave p % 16 adds the squares of its outputs in turn, 16 partials, 1 / sqrtf, product."""
+    n, D = x.shape
+    P = proj.shape[0]
+    eps = F32(eps)
+    xp = np.zeros((n, 1024), F32)
+    xp[:, :D] = x
+
+    def block_total(v):   # [n, 1024] -> [n]
+        return _seq_sum(_butterfly(v.reshape(n, 16, 64))[:, :, 0])
+
+    mean = _f32(block_total(xp) / F32(D))[:, None]
+    c = np.where(np.arange(1024) < D, _f32(xp - mean), F32(0))
+    if mutation == "single_pass":
+        var = _f32(_f32(block_total(_f32(xp * xp)) / F32(D)) - _f32(mean[:, 0] * mean[:, 0]))
+    else:
+        var = _f32(block_total(_f32(c * c)) / F32(D))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if mutation == "eps_outside":
+            rstd = _f32(F32(1) / _f32(np.sqrt(var) + eps))
+        else:
+            rstd = _f32(F32(1) / np.sqrt(_f32(var + eps)))
+        y = _f32(_f32(_f32(c[:, :D] * rstd[:, None]) * g) + b)
+    if mutation == "y_bf16":
+        y = eb.round_to(y, "bf16")
+    a = np.zeros((n, P, 64), F32)
+    lane = np.arange(64)
+    for i in range((D + 255) // 256):
+        for j in range(4):
+            d = lane * 4 + 256 * i + j
+            ok = lane * 4 + 256 * i < D
+            dd = np.where(ok, d, 0)
+            term = proj[:, dd].astype(np.float64)[None, :, :] * y[:, dd].astype(np.float64)[:, None, :]
+            a = np.where(ok, _f32(term + a), a)
+    o = _butterfly(a)[:, :, 0]                                         # [n, P]
+    if not normalize:
+        return o
+    osq = eb.round_to(o, "fp16") if mutation == "norm_fp16" else o
+    sq = np.zeros((n, 16), F32)
+    for p in range(P):
+        sq[:, p % 16] = _f32(sq[:, p % 16] + _f32(osq[:, p] * osq[:, p]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rn = _f32(F32(1) / np.sqrt(_seq_sum(sq)))
+        return _f32(o * rn[:, None])
+
+
+POOL_CASES = [(64, 1), (320, 17), (512, 64), (768, 512), (1020, 768), (1024, 1024)]
+
+
+@pytest.mark.parametrize("D,P", POOL_CASES)
+def test_pool_project_emulation_within_budget(D, P):
+    x = ends._pool_rows(25, D, D)
+    g, b, proj = ends._pool_params(D, P, D + P)
+    for normalize in (False, True):
+        ref, bud = eb.pool_project_budget(x, g, b, proj, normalize)
+        assert np.isfinite(bud).all()
+        r = eb.worst(_pool_emulate(x, g, b, proj, normalize), ref, bud)[0]
+        print(f"pool D={D} P={P} normalize={normalize}: {r:.3g}")
+        assert r <= 1.0, (D, P, normalize, r)
+
+
+@pytest.mark.parametrize("mutation", ["single_pass", "eps_outside", "y_bf16", "norm_fp16"])
+def test_pool_project_mutations_break_the_budget(mutation):
+    """E[x^2] - mean^2 (shows on the rows of mean 1e3), eps added to the standard deviation instead of the variance, the
+    projection fed a bf16-rounded y, the norm taken from fp16-rounded outputs."""
+    for D, P in ((512, 64), (768, 512), (1024, 768)):
+        x = ends._pool_rows(25, D, D)
+        g, b, proj = ends._pool_params(D, P, D + P)
+        ref, bud = eb.pool_project_budget(x, g, b, proj, True)
+        with np.errstate(invalid="ignore"):
+            r = eb.worst(_pool_emulate(x, g, b, proj, True, mutation), ref, bud)[0]
+        print(f"pool {mutation} D={D} P={P}: budget ratio {r:.3g}")
+        assert r > 1.0, (mutation, D, P, r)
+
+
+def test_pool_project_zero_norm_has_no_finite_budget():
+    """gamma = beta = 0: the output is 0 and its norm 0; the kernel returns 0 * inf, the reference x / x.norm() is 0 / 0: the
+    one case excluded from the budgets (pinned on the GPU as well)."""
+    x = ends._pool_rows(5, 512, 1)
+    z = np.zeros(512, F32)
+    proj = ends._pool_params(512, 64, 0)[2]
+    assert (_pool_emulate(x, z, z, proj, False) == 0).all()
+    with np.errstate(invalid="ignore"):
+        assert np.isnan(_pool_emulate(x, z, z, proj, True)).all()
+    assert np.isinf(eb.pool_project_budget(x, z, z, proj, True)[1]).all()
+
+
+def test_eos_taken_as_the_last_argmax_breaks_the_pool_budget():
+    """Prompts padded with the EOS id: the pooled row is the FIRST position of the largest id."""
+    rng = np.random.default_rng(0)
+    K, S, D, P = 4, 16, 128, 64
+    ids = rng.integers(1, 1000, size=(K, S))
+    for k in range(K):
+        ids[k, 5 + k:] = 49407
+    assert list(eb.eos_rows(ids)) == [k * S + 5 + k for k in range(K)]
+    last = np.arange(K) * S + (S - 1 - ids[:, ::-1].argmax(axis=1))
+    x = rng.standard_normal((K * S, D)).astype(F32)
+    g, b, proj = ends._pool_params(D, P, 1)
+    ref, bud = eb.pool_project_budget(x[eb.eos_rows(ids)], g, b, proj, True)
+    assert eb.worst(_pool_emulate(x[eb.eos_rows(ids)], g, b, proj, True), ref, bud)[0] <= 1.0
+    r = eb.worst(_pool_emulate(x[last], g, b, proj, True), ref, bud)[0]
+    print(f"EOS as the last argmax: budget ratio {r:.3g}")
+    assert r > 1.0
+
+
+def _bank_emulate(f, K, T, acc16=False):
+    P = f.shape[1]
+    f = f.reshape(K, T, P)
+    a = np.zeros((K, P), F32)
+    for t in range(T):
+        a = eb.round_to(a + f[:, t], "fp16") if acc16 else _f32(a + f[:, t])
+    a = _f32(a / F32(T))
+    lanes = np.zeros((K, 64), F32)
+    for d in range(P):
+        lanes[:, d % 64] = _f32(lanes[:, d % 64] + _f32(a[:, d] * a[:, d]))
+    rn = _f32(F32(1) / np.sqrt(_butterfly(lanes)[:, 0]))
+    return _f32(a * rn[:, None])
+
+
+@pytest.mark.parametrize("P", [64, 512, 768])
+def test_bank_reduce_emulation_within_budget_and_fp16_mean_breaks_it(P):
+    for K, T in ((1, 1), (3, 7), (5, 80)):
+        f = ends._bank_rows(K, T, P, K + T + P)
+        ref, bud = eb.bank_reduce_budget(f, K, T)
+        assert np.isfinite(bud).all()
+        r = eb.worst(_bank_emulate(f, K, T), ref, bud)[0]
+        assert r <= 1.0, (P, K, T, r)
+        if T > 1:
+            r_bad = eb.worst(_bank_emulate(f, K, T, acc16=True), ref, bud)[0]
+            print(f"bank P={P} K={K} T={T}: correct {r:.3g}, mean accumulated in fp16 {r_bad:.3g}")
+            assert r_bad > 1.0

@@ -353,7 +353,7 @@ def test_prompt_ensemble_bank():
 def test_patch_gemm_gathering_pixels_equals_the_patchify_route(name, batches, precision):
     """SURVEY.md K1, the im2col-free patch embedding: since round 4 the patch GEMM reads its A operand from the fp32 NCHW
     pixels itself (gemm_p256_kernel<..., PXF>) wherever the persistent kernel takes the problem and the patch size divides
-    a K-step (B/16, B/32 from batch 56 / 223 on).  Against the rounds 1 - 3 route (patchify writes a patch matrix, the GEMM
+    a K-step (B/16, B/32 from batch 55 / 220 on with 256 CUs: DESIGN.md 2.4).  Against the rounds 1 - 3 route (patchify writes a patch matrix, the GEMM
     reads it back; harness switch mcm_debug_patch_fold(0)): the same bits, whole and ragged batches, every dtype; and
     ViT-L/14 (P = 14, padded K) and small batches keep the old route."""
     from mcm_amd.engine import NativeCLIP
