@@ -46,7 +46,10 @@ def process_args(argv=None):
     p.add_argument("-b", "--batch-size", default=512, type=int, help="mini-batch size")
     p.add_argument("--T", type=int, default=1, help="temperature parameter")
     p.add_argument("--model", default="CLIP", type=str, help="model architecture")
-    p.add_argument("--CLIP_ckpt", type=str, default="ViT-B/16", choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px"],
+    p.add_argument("--CLIP_ckpt", type=str, default="ViT-B/16",
+                   choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px",
+                            # OpenCLIP-trained (LAION-2B) checkpoints in HF layout: the exact GELU in both towers
+                            "ViT-B/32-laion2b", "ViT-B/16-laion2b", "ViT-L/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
                    choices=["MCM", "energy", "max-logit", "entropy", "var", "maha"], help="score options")

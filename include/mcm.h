@@ -29,13 +29,16 @@
 extern "C" {
 #endif
 
-#define MCM_ABI_VERSION 4 /* 2: mcm_set_weight takes the host element type; mcm_config.weight_operands; split-weight
+#define MCM_ABI_VERSION 5 /* 2: mcm_set_weight takes the host element type; mcm_config.weight_operands; split-weight
                           * arm and mcm_weights_operand_exact; mcm_op_linear_ex / mcm_op_split_weight; the round-2
                           * mcm_debug_* exports live in libmcm_hip_harness.so only
                           * 3: MCM_KC_COUNT 7 -> 11 (per-shape GEMM classes: mcm_profile_read's arrays grew); the
                           * split-activation arm (mcm_score_x2 ...) and the MCM_LINEAR_SPLIT_X / _OUT flags
                           * 4: mcm_config.x2_max_batch (the split-activation workspace is sized by the caller);
-                          * mcm_kernel_faults + the sticky fault word (every wait of a persistent kernel is bounded) */
+                          * mcm_kernel_faults + the sticky fault word (every wait of a persistent kernel is bounded)
+                          * 5: mcm_config.v_hidden_act / t_hidden_act (MCM_ACT_*: the MLP activation is a property of the
+                          * model; 0 = QuickGELU as before, 1 = exact erf GELU for OpenCLIP-trained checkpoints) and the
+                          * MCM_LINEAR_ACT_GELU flag of mcm_op_linear_ex */
 
 /* error codes */
 #define MCM_OK 0
@@ -71,6 +74,13 @@ extern "C" {
                               * the operand dtype (counted on the device in mcm_finalize_weights)               */
 #define MCM_WEIGHTS_SINGLE 1 /* one rounded operand whatever the values (rounds 1 - 3 behaviour)                 */
 #define MCM_WEIGHTS_SPLIT 2  /* always the split form                                                            */
+
+/* MLP activation of a tower (cfg.v_hidden_act / cfg.t_hidden_act) = the `hidden_act` of HF's CLIPVisionConfig /
+ * CLIPTextConfig.  OpenAI's checkpoints were trained with QuickGELU; the OpenCLIP-trained ones (LAION-2B, DataComp) that load
+ * into the same CLIPModel — same shapes, same state-dict names — with the exact GELU.  The shapes cannot tell them apart: a
+ * checkpoint scored with the other activation gives plausible, wrong scores (the two differ by up to 0.020 per element). */
+#define MCM_ACT_QUICK_GELU 0 /* x * sigmoid(1.702 x)   (activations.py QuickGELUActivation; "quick_gelu")         */
+#define MCM_ACT_GELU 1       /* x * Phi(x), erf form   (activations.py GELUActivation = torch gelu; "gelu")        */
 
 /* score kinds — the epilogues of utils/detection_util.py:233-248 */
 #define MCM_SCORE_MCM 0       /* -max_k softmax(cos/T)             (:236,:248) */
@@ -111,6 +121,8 @@ typedef struct mcm_config {
                              * activation buffers at twice the bytes: +1.5 GB at ViT-B/16 batch 512), n > 0 = at most n (the
                              * buffers hold max(max_batch rows, 2 x the rows of n images): nothing extra for n <= max_batch / 2),
                              * < 0 = no split-activation workspace (those calls return MCM_EINVAL)  */
+  int32_t v_hidden_act;     /* MCM_ACT_* of the vision tower's MLPs (ABI 5; 0 = QuickGELU: a zeroed struct is an OpenAI model) */
+  int32_t t_hidden_act;     /* MCM_ACT_* of the text tower's MLPs; anything but the two values: MCM_EINVAL from mcm_create */
 } mcm_config;
 
 int mcm_abi_version(void);
@@ -364,6 +376,9 @@ int mcm_op_linear(mcm_handle* h, int32_t prec, const void* x_dev, const void* w_
  * Together they are the GEMMs of the split-activation arm (mcm_score_x2). */
 #define MCM_LINEAR_SPLIT_X 2
 #define MCM_LINEAR_SPLIT_OUT 4
+/* bit 3 (ABI 5; epilogue 1 only, every mode): the activation is the exact erf GELU (MCM_ACT_GELU) instead of QuickGELU — the
+ * fc1 epilogue of a tower whose hidden_act is "gelu".  Combines with the three bits above exactly as epilogue 1 does. */
+#define MCM_LINEAR_ACT_GELU 8
 int mcm_op_linear_ex(mcm_handle* h, int32_t prec, const void* x_dev, const void* w_dev,
                      const float* bias_dev, void* y_dev, float* resid_dev, int32_t M, int32_t N,
                      int32_t K, int32_t epi, int32_t flags, void* stream);
@@ -423,6 +438,10 @@ int mcm_kernel_faults(const mcm_handle* h);
  * Removed in round 6 after measuring negative (EXPERIMENTS.md "Removed arms"): 1/2 persistent 256x128 3-stage, 6 the ping-pong
  * loop on 32x32x16 MFMAs, 7 balanced DMA, 8 staggered epilogues.  Returns MCM_OK, or MCM_EINVAL for an unknown variant. */
 int mcm_debug_gemm_variant(int32_t variant);
+/* The MLP activations exactly as the GEMM epilogues compute them, element-wise: y[i] = act(x[i]) for n fp32 values on the device.
+ * act: 0 = QuickGELU with the IEEE division (fp32 arm, split outputs), 1 = its v_exp / v_rcp form (16-bit outputs), 2 = the erf
+ * GELU (every mode).  Asynchronous on `stream`. */
+int mcm_debug_op_act(mcm_handle* h, int32_t act, const float* x_dev, float* y_dev, int64_t n, void* stream);
 /* 16-bit attention kernel: 1 = the shipped policy (the transpose-read kernel; its persistent form at the B/16 shape from 16 jobs
  * per CU on), 0 = the round-1 kernel, 10 = XCD-aware deal of the (sequence, head) workgroups, 11 = the q-blocks dealt to the waves
  * rotated per workgroup (SIMD balance; bit-identical, no gain), 21 = the persistent form at every size and query count of the

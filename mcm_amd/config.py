@@ -11,12 +11,13 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass, asdict, replace
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 PREC_BF16 = 0
 PREC_F32 = 1
 PREC_F16 = 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2                       # include/mcm.h MCM_DT_*
 WEIGHT_OPERANDS = {"auto": 0, "single": 1, "split": 2}  # include/mcm.h MCM_WEIGHTS_*
+HIDDEN_ACTS = {"quick_gelu": 0, "gelu": 1}              # include/mcm.h MCM_ACT_*: HF `hidden_act` -> mcm_config.*_hidden_act
 
 SCORE_KINDS = {"MCM": 0, "max-logit": 1, "energy": 2, "entropy": 3, "var": 4}
 
@@ -54,6 +55,8 @@ class CConfig(ctypes.Structure):
         ("max_prompt_tokens", ctypes.c_int32),
         ("weight_operands", ctypes.c_int32),
         ("x2_max_batch", ctypes.c_int32),
+        ("v_hidden_act", ctypes.c_int32),
+        ("t_hidden_act", ctypes.c_int32),
     ]
 
 
@@ -74,6 +77,10 @@ class ClipGeometry:
     t_mlp: int = 2048
     proj_dim: int = 512
     ln_eps: float = 1e-5
+    # MLP activation of each tower = HF `vision_config.hidden_act` / `text_config.hidden_act`: "quick_gelu" (OpenAI's
+    # checkpoints) or "gelu" (the exact erf form: the OpenCLIP-trained checkpoints).  The shapes are the same either way.
+    v_hidden_act: str = "quick_gelu"
+    t_hidden_act: str = "quick_gelu"
 
     @property
     def n_patches(self) -> int:
@@ -130,6 +137,10 @@ class ClipGeometry:
              max_prompt_tokens: int = 1024 * 77, weight_operands: int = 0, x2_max_batch: int = 0) -> CConfig:
         d = asdict(self)
         d.pop("name")
+        for k in ("v_hidden_act", "t_hidden_act"):
+            if d[k] not in HIDDEN_ACTS:
+                raise ValueError(f"{self.name}: {k} = {d[k]!r}; the kernels have {sorted(HIDDEN_ACTS)}")
+            d[k] = HIDDEN_ACTS[d[k]]
         return CConfig(abi_version=ABI_VERSION, device=device, precision=precision,
                        max_batch=max_batch, max_prompt_tokens=max_prompt_tokens,
                        weight_operands=weight_operands, x2_max_batch=x2_max_batch, **d)
@@ -144,13 +155,13 @@ class ClipGeometry:
                              intermediate_size=self.t_mlp, num_hidden_layers=self.t_layers,
                              num_attention_heads=self.t_heads,
                              max_position_embeddings=self.max_positions,
-                             hidden_act="quick_gelu", layer_norm_eps=self.ln_eps,
+                             hidden_act=self.t_hidden_act, layer_norm_eps=self.ln_eps,
                              projection_dim=self.proj_dim, eos_token_id=49407,
                              bos_token_id=49406, pad_token_id=49407),
             vision_config=dict(hidden_size=self.v_width, intermediate_size=self.v_mlp,
                                num_hidden_layers=self.v_layers,
                                num_attention_heads=self.v_heads, image_size=self.image_size,
-                               patch_size=self.patch_size, hidden_act="quick_gelu",
+                               patch_size=self.patch_size, hidden_act=self.v_hidden_act,
                                layer_norm_eps=self.ln_eps, projection_dim=self.proj_dim),
             projection_dim=self.proj_dim,
         )
@@ -168,11 +179,21 @@ CHECKPOINTS = {
     "ViT-L/14@336px": ClipGeometry("ViT-L/14@336px", image_size=336, patch_size=14, v_width=1024, v_heads=16, v_layers=24,
                                    v_mlp=4096, t_width=768, t_heads=12, t_mlp=3072, proj_dim=768),
 }
+# not reference choices either: the OpenCLIP-trained (LAION-2B) checkpoints that load into the same HF CLIPModel — the
+# geometry of their OpenAI namesakes, state-dict names included, and the exact GELU in both towers
+for _name in ("ViT-B/32", "ViT-B/16", "ViT-L/14"):
+    CHECKPOINTS[_name + "-laion2b"] = replace(CHECKPOINTS[_name], name=_name + "-laion2b", v_hidden_act="gelu", t_hidden_act="gelu")
+del _name
 HUB_IDS = {
     "ViT-B/32": "openai/clip-vit-base-patch32",
     "ViT-B/16": "openai/clip-vit-base-patch16",
     "ViT-L/14": "openai/clip-vit-large-patch14",
     "ViT-L/14@336px": "openai/clip-vit-large-patch14-336",
+    # UNVERIFIED: written from memory, no hub was reachable to check them against (they only name the tokenizer files'
+    # origin and the log line; weights come from --weights)
+    "ViT-B/32-laion2b": "laion/CLIP-ViT-B-32-laion2B-s34B-b79K",
+    "ViT-B/16-laion2b": "laion/CLIP-ViT-B-16-laion2B-s34B-b88K",
+    "ViT-L/14-laion2b": "laion/CLIP-ViT-L-14-laion2B-s32B-b82K",
 }
 
 # Reduced geometries for fast parity tests: full-width heads (head_dim 64) and every code
@@ -185,6 +206,9 @@ TEST_GEOMETRIES = {
                          v_layers=2, v_mlp=512, vocab_size=49408, max_positions=77,
                          t_width=128, t_heads=2, t_layers=2, t_mlp=512, proj_dim=64),
 }
+# the same two with the exact GELU in both towers (the OpenCLIP-trained family)
+TEST_GEOMETRIES["tiny-gelu"] = replace(TEST_GEOMETRIES["tiny"], name="tiny-gelu", v_hidden_act="gelu", t_hidden_act="gelu")
+TEST_GEOMETRIES["B16-2L-gelu"] = replace(TEST_GEOMETRIES["B16-2L"], name="B16-2L-gelu", v_hidden_act="gelu", t_hidden_act="gelu")
 
 
 def geometry(name: str) -> ClipGeometry:

@@ -142,6 +142,31 @@ __device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + __expf
 __device__ __forceinline__ float quick_gelu_fast(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x));
 }
+// GELU in its exact (erf) form, x * Phi(x): what HF's GELUActivation / torch gelu compute and what the OpenCLIP-trained
+// checkpoints carry as hidden_act "gelu".  Phi comes from the complementary side, so that nothing cancels in the negative
+// tail (0.5 x (1 + erf(x / sqrt 2)) loses every digit below x ~ -5.5):
+//   h(|x|) = 0.5 erfc(|x| / sqrt 2) = t P(t) exp(-x^2 / 2),  t = 1 / (1 + 0.39 |x| / sqrt 2),  Phi = x >= 0 ? 1 - h : h
+// P: degree 5, a minimax fit of this file's own (|h - fit| <= 6.0e-9 = 0.10 u32 on the whole axis with the fp32 constants
+// below, tests/test_gelu_budget.py::test_fit_error_of_the_polynomial; Abramowitz & Stegun
+// 7.1.26 is the same form one degree lower at 1.5e-7).  What is left is the fp32 arithmetic: |error| <= 6 u32 |x| by
+// analysis (the rounding of 1 + p|x| and of the 1-ulp v_rcp_f32 reach h with a factor 1.45 each), 3.7 u32 |x| measured in
+// emulation, against 6.4 for torch's own fp32 gelu.  One v_rcp_f32, one v_exp_f32, 13 VALU; no branch, no division, and
+// every finite x gives a finite result (x^2 = inf -> exp2(-inf) = 0 -> h = 0).  The ONE form of every precision mode and
+// every kernel variant: a 16-bit arm has no cheaper form of its own (tests/gelu_budget.py).
+__device__ __forceinline__ float gelu_erf(float x) {
+#pragma clang fp contract(off)  // explicit fmas only: the same bits at every call site
+  const float ax = __builtin_fabsf(x);
+  const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(ax, 0.2757716477f, 1.0f));
+  const float e = __builtin_amdgcn_exp2f((ax * ax) * -0.7213475204f);  // exp(-x^2 / 2)
+  float h = -0.11376846582f;
+  h = __builtin_fmaf(h, t, 0.44333177805f);
+  h = __builtin_fmaf(h, t, -0.31769949198f);
+  h = __builtin_fmaf(h, t, 0.32477918267f);
+  h = __builtin_fmaf(h, t, 0.045694414526f);
+  h = __builtin_fmaf(h, t, 0.11766257882f);
+  h = (h * t) * e;
+  return x * (x >= 0.0f ? 1.0f - h : h);
+}
 
 // wave64 butterfly reductions
 __device__ __forceinline__ float wave_sum(float v) {
@@ -223,10 +248,17 @@ enum GemmEpi : int {
   // the next GEMM's X operand — out[M, 2N]: per 64 columns hi[64] = round(v) then lo[64] = round(v - hi)
   EPI_STORE_X2 = 4,
   EPI_GELU_X2 = 5,  // QuickGELU in its exact form (the fp32 arm's), then split
+  // the MLP activation of a tower whose hidden_act is "gelu" (mcm_config.v_hidden_act / t_hidden_act = MCM_ACT_GELU): the
+  // twins of EPI_GELU / EPI_GELU_X2 with gelu_erf.  Shipped kernels only: no A/B arm of gemm_arms.hpp takes them.
+  EPI_GELU_ERF = 6,     // out = GELU(acc + bias), erf form
+  EPI_GELU_ERF_X2 = 7,  // the same, then split
 };
-__host__ __device__ constexpr bool epi_x2(int e) { return e == EPI_STORE_X2 || e == EPI_GELU_X2; }
-__host__ __device__ constexpr bool epi_store16(int e) { return e <= EPI_GELU || epi_x2(e); }  // 16-bit [M, N] / [M, 2N] outputs
-__host__ __device__ constexpr bool epi_gelu(int e) { return e == EPI_GELU || e == EPI_GELU_X2; }
+// the predicates name every member: nothing may depend on the numeric order of the values
+__host__ __device__ constexpr bool epi_x2(int e) { return e == EPI_STORE_X2 || e == EPI_GELU_X2 || e == EPI_GELU_ERF_X2; }
+__host__ __device__ constexpr bool epi_erf(int e) { return e == EPI_GELU_ERF || e == EPI_GELU_ERF_X2; }
+__host__ __device__ constexpr bool epi_gelu(int e) { return e == EPI_GELU || e == EPI_GELU_X2 || epi_erf(e); }  // any activation
+__host__ __device__ constexpr bool epi_plain16(int e) { return e == EPI_STORE || e == EPI_GELU || e == EPI_GELU_ERF; }  // 16-bit [M, N]
+__host__ __device__ constexpr bool epi_store16(int e) { return epi_plain16(e) || epi_x2(e); }  // 16-bit [M, N] / [M, 2N] outputs
 
 struct GemmArgs {
   const void* x;      // [M, K] operand dtype, row stride ldx elements

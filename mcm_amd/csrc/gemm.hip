@@ -139,7 +139,9 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, const f32x4_t (
       if constexpr (epi_gelu(EPI)) {  // same form in every kernel variant: results must not
 #pragma unroll                        // depend on which variant the size heuristic picks
         for (int t = 0; t < 4; ++t)
-          v[fj][t] = (PREC != MCM_PREC_F32 && !epi_x2(EPI)) ? quick_gelu_fast(v[fj][t]) : quick_gelu(v[fj][t]);
+          v[fj][t] = epi_erf(EPI)                                ? gelu_erf(v[fj][t])
+                     : (PREC != MCM_PREC_F32 && !epi_x2(EPI)) ? quick_gelu_fast(v[fj][t])
+                                                              : quick_gelu(v[fj][t]);
       }
     }
     if constexpr (epi_x2(EPI)) {  // split image: the lane's 16 columns as hi[16] at split_col(n), lo[16] 64 elements on
@@ -239,7 +241,7 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, const f32x4
         f32x4_t v = acc[fj][u] + bv[fj];
         if constexpr (epi_gelu(EPI)) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = quick_gelu(v[t]);
+          for (int t = 0; t < 4; ++t) v[t] = epi_erf(EPI) ? gelu_erf(v[t]) : quick_gelu(v[t]);
         }
         sat_track<PREC>(amax, v[0], v[1]);
         sat_track<PREC>(amax, v[2], v[3]);
@@ -263,7 +265,7 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, const f32x4
         }
       }
     }
-  } else if constexpr (PREC != MCM_PREC_F32 && EPI <= EPI_GELU) {
+  } else if constexpr (PREC != MCM_PREC_F32 && epi_plain16(EPI)) {
     // 16-row units ping-pong between the two 2-KiB halves of the window: unit u is converted and
     // written while unit u-1 is read back and stored, so the LDS round trip and the store issue
     // (a 1-KiB store blocks its wave like an LDS-DMA piece does) overlap the next unit's VALU work.
@@ -274,9 +276,9 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, const f32x4
 #pragma unroll
       for (int fj = 0; fj < 4; ++fj) {
         v[fj] = acc[fj][u] + bv[fj];
-        if constexpr (EPI == EPI_GELU) {
+        if constexpr (epi_gelu(EPI)) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) v[fj][t] = quick_gelu_fast(v[fj][t]);
+          for (int t = 0; t < 4; ++t) v[fj][t] = epi_erf(EPI) ? gelu_erf(v[fj][t]) : quick_gelu_fast(v[fj][t]);
         }
         sat_track<PREC>(amax, v[fj][0], v[fj][1]);
         sat_track<PREC>(amax, v[fj][2], v[fj][3]);
@@ -377,9 +379,9 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, const f32x4
 #pragma unroll
       for (int fj = 0; fj < 4; ++fj) {
         f32x4_t v = acc[fj][c] + bv[fj];
-        if constexpr (EPI == EPI_GELU) {
+        if constexpr (epi_gelu(EPI)) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) v[t] = quick_gelu(v[t]);
+          for (int t = 0; t < 4; ++t) v[t] = epi_erf(EPI) ? gelu_erf(v[t]) : quick_gelu(v[t]);
         }
         *(f32x4_t*)(scratch + fr * 256 + (((g * 4 + fj) ^ sw) << 4)) = v;
       }
@@ -675,7 +677,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p256_kernel(const GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ES = prec_esize(PREC);
   // store instructions per wave per full tile: 8 rows x (2 x 16 B bf16 | 4 x 16 B fp32)
-  constexpr int STORES_PER_EPI = (PREC != MCM_PREC_F32 && EPI <= EPI_GELU) ? 16 : 32;  // (*_X2: 32 as well)
+  constexpr int STORES_PER_EPI = (PREC != MCM_PREC_F32 && epi_plain16(EPI)) ? 16 : 32;  // (*_X2: 32 as well)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // 0..7
 
@@ -943,9 +945,9 @@ __device__ __forceinline__ void wave_epilogue_f32_interior(const GemmArgs& a, co
     for (int fj = 0; fj < 4; ++fj) {
       f32x4_t v = acc[fj][c];
       if constexpr (EPI != EPI_RESID) v += bv[fj];
-      if constexpr (EPI == EPI_GELU) {
+      if constexpr (epi_gelu(EPI)) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) v[t] = quick_gelu(v[t]);
+        for (int t = 0; t < 4; ++t) v[t] = epi_erf(EPI) ? gelu_erf(v[t]) : quick_gelu(v[t]);
       }
       *(f32x4_t*)(scratch + fr * 256 + (((g * 4 + fj) ^ fr) << 4)) = v;
     }
@@ -1354,12 +1356,14 @@ template <int PREC, int EPI>
 hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
   int v = size_policy(a.M, a.N);
 #ifdef MCM_ARMS
-  {  // A/B builds: the LayerNorm fold / tail forms and the forced arm variants (gemm_arms.hpp)
+  if constexpr (epi_erf(EPI)) {  // the erf epilogue lives in the shipped kernels only: an arm would apply QuickGELU (or nothing)
+    if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk || v == 9) return hipErrorInvalidValue;  // (9: the arms' ping-pong text)
+  } else {  // A/B builds: the LayerNorm fold / tail forms and the forced arm variants (gemm_arms.hpp)
     hipError_t e;
     if (arms::route<PREC, EPI>(v, a, s, &e)) return e;
   }
 #else
-  if (a.fold_z || a.fold_rs || a.ln_y) return hipErrorInvalidValue;  // A/B arms: not in the shipped library
+  if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk) return hipErrorInvalidValue;  // A/B arms: not in the shipped library
 #endif
   if constexpr (EPI == EPI_PATCH) {
     if (a.px) return launch_p256<PREC, EPI, false, true>(a, s);  // the pixel-gathering form of the persistent kernel
@@ -1403,8 +1407,10 @@ hipError_t launch_prec(int epi, const GemmArgs& a, hipStream_t s) {
   switch (epi) {
     case EPI_STORE_X2: return launch_one_x2<PREC, EPI_STORE_X2>(a, s);
     case EPI_GELU_X2: return launch_one_x2<PREC, EPI_GELU_X2>(a, s);
+    case EPI_GELU_ERF_X2: return launch_one_x2<PREC, EPI_GELU_ERF_X2>(a, s);
     case EPI_STORE: return launch_one<PREC, EPI_STORE>(a, s);
     case EPI_GELU: return launch_one<PREC, EPI_GELU>(a, s);
+    case EPI_GELU_ERF: return launch_one<PREC, EPI_GELU_ERF>(a, s);
     case EPI_RESID: return launch_one<PREC, EPI_RESID>(a, s);
     case EPI_PATCH: return launch_one<PREC, EPI_PATCH>(a, s);
   }
@@ -1464,7 +1470,7 @@ bool gemm_patch_takes_pixels(int prec, int M, int N, int kpad, int patch, int im
 }
 
 int gemm_fold_kind(int epi, int M, int N) {
-  if (epi == EPI_PATCH || M <= 0 || N <= 0) return 0;
+  if (epi == EPI_PATCH || epi_erf(epi) || M <= 0 || N <= 0) return 0;  // (the fold's consumer epilogue is QuickGELU's)
   const int v = size_policy(M, N);
   if (v == 5 && M % p256::BM == 0 && N % p256::BN == 0) return 1;
   if (v == 0) return 2;
@@ -1505,8 +1511,8 @@ hipError_t launch_gemm(int prec, int epi, const GemmArgs& a_in, hipStream_t s) {
     return hipErrorInvalidValue;
   if (a.xsplit && a.ldx % 128) return hipErrorInvalidValue;
   if (epi_x2(epi) && (a.N % 64 || a.ldo % 128)) return hipErrorInvalidValue;
-  // head-major outputs: 16-bit store epilogues only, whole 64-column blocks
-  if (a.hm && (a.hm < a.M || a.N % 64 || epi > EPI_GELU || prec == MCM_PREC_F32)) return hipErrorInvalidValue;
+  // head-major outputs: the 16-bit store epilogues of the A/B arm only (bias, QuickGELU), whole 64-column blocks
+  if (a.hm && (a.hm < a.M || a.N % 64 || !(epi == EPI_STORE || epi == EPI_GELU) || prec == MCM_PREC_F32)) return hipErrorInvalidValue;
 #ifndef MCM_HARNESS
   if (a.hm) return hipErrorInvalidValue;  // the head-major store path exists in the harness library only
 #endif

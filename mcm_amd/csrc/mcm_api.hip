@@ -48,6 +48,7 @@ struct Tower {
   int prec = MCM_PREC_BF16;  // operand mode of this tower's GEMMs / attention / LayerNorm output
   std::vector<LayerW> L;
   bool split = false;        // GEMM weights held as W_hi + W_lo (GemmArgs::ksplit; include/mcm.h MCM_WEIGHTS_*)
+  int act = MCM_ACT_QUICK_GELU;  // MLP activation (mcm_config.v_hidden_act / t_hidden_act): which fc1 epilogue run_layers asks for
 };
 
 struct EvPair {
@@ -217,7 +218,7 @@ int g_nsplit = 1;  // A/B (mcm_debug_nsplit): the wide store GEMMs (QKV, fc1) as
 hipError_t gemm(mcm_handle* h, hipStream_t s, int prec, int epi, const GemmArgs& a_in) {
   GemmArgs a = a_in;
 #ifdef MCM_HARNESS
-  if (g_nsplit > 1 && epi <= EPI_GELU && a.N >= 2048 && a.N % (256 * g_nsplit) == 0 && !a.fold_rs && !a.hm && a.M > 4096) {
+  if (g_nsplit > 1 && (epi == EPI_STORE || epi == EPI_GELU) && a.N >= 2048 && a.N % (256 * g_nsplit) == 0 && !a.fold_rs && !a.hm && a.M > 4096) {
     // W re-fetch experiment: the XCD's L2 (4 MiB) cannot hold all of W (fc1: 4.7 MB) beside the X
     // panels in flight, so W streams through it once per tile round; with the columns cut in n blocks only N / n of W
     // is live per launch (X is then read n times).  Same bits (a column's K-sum does not depend on its neighbours).
@@ -394,8 +395,10 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
   const int Mp = (int)padded_rows(h, M);
   const int ks = t.split ? 1 : 0;
   const int xs = x2 ? 1 : 0;
-  const int epi_store = x2 ? EPI_STORE_X2 : EPI_STORE, epi_act = x2 ? EPI_GELU_X2 : EPI_GELU;
-  if (x2) fold_ok = false;
+  const bool erf = t.act == MCM_ACT_GELU;  // the tower's MLP activation: exact GELU (OpenCLIP-trained) or QuickGELU (OpenAI)
+  const int epi_store = x2 ? EPI_STORE_X2 : EPI_STORE;
+  const int epi_act = erf ? (x2 ? EPI_GELU_ERF_X2 : EPI_GELU_ERF) : (x2 ? EPI_GELU_X2 : EPI_GELU);
+  if (x2 || erf) fold_ok = false;  // (the LayerNorm fold's consumer epilogue is an A/B arm: QuickGELU only)
   const size_t wrow = (size_t)D * es * (t.split ? 2 : 1);  // bytes per row of a [*, D] weight image
   // producer form: 1 = fused into the residual GEMM's epilogue (ping-pong kernel), 2 = plain residual GEMM + fold_rows
   // (tile kernel: small batches) - bit-identical; the consumers need a fold epilogue in whichever kernel they take
@@ -616,6 +619,9 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
     return fail(nullptr, MCM_EINVAL, "unknown precision");
   if (c.weight_operands < MCM_WEIGHTS_AUTO || c.weight_operands > MCM_WEIGHTS_SPLIT)
     return fail(nullptr, MCM_EINVAL, "unknown weight_operands");
+  if ((c.v_hidden_act != MCM_ACT_QUICK_GELU && c.v_hidden_act != MCM_ACT_GELU) ||
+      (c.t_hidden_act != MCM_ACT_QUICK_GELU && c.t_hidden_act != MCM_ACT_GELU))
+    return fail(nullptr, MCM_EINVAL, "unknown hidden_act (MCM_ACT_QUICK_GELU or MCM_ACT_GELU)");
   if (c.v_heads <= 0 || c.t_heads <= 0 || c.v_width != c.v_heads * 64 || c.t_width != c.t_heads * 64)
     return fail(nullptr, MCM_EINVAL, "head_dim must be 64");
   if (c.patch_size <= 0 || c.image_size % c.patch_size)
@@ -649,6 +655,8 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
   // instead of averaging out.  cfg.precision selects the vision tower's operand mode.
   h->vis = Tower{c.v_width, c.v_heads, c.v_layers, c.v_mlp, c.precision, {}};
   h->txt = Tower{c.t_width, c.t_heads, c.t_layers, c.t_mlp, MCM_PREC_F32, {}};
+  h->vis.act = c.v_hidden_act;
+  h->txt.act = c.t_hidden_act;
 
   // parameter registry (HF state_dict names)
   add_param(h, "vision_model.embeddings.class_embedding", {c.v_width});
@@ -1355,15 +1363,19 @@ int mcm_op_linear_ex(mcm_handle* h, int32_t prec, const void* x_dev, const void*
   if (!h) return MCM_EINVAL;
   if (epi < EPI_STORE || epi > EPI_RESID) return fail(h, MCM_EINVAL, "bad epilogue");
   const bool split = (flags & MCM_LINEAR_SPLIT_W) != 0, xs = (flags & MCM_LINEAR_SPLIT_X) != 0, os = (flags & MCM_LINEAR_SPLIT_OUT) != 0;
-  if ((flags & ~(MCM_LINEAR_SPLIT_W | MCM_LINEAR_SPLIT_X | MCM_LINEAR_SPLIT_OUT)) || (split && (prec == MCM_PREC_F32 || K % 64)))
+  const bool erf = (flags & MCM_LINEAR_ACT_GELU) != 0;
+  if ((flags & ~(MCM_LINEAR_SPLIT_W | MCM_LINEAR_SPLIT_X | MCM_LINEAR_SPLIT_OUT | MCM_LINEAR_ACT_GELU)) ||
+      (split && (prec == MCM_PREC_F32 || K % 64)))
     return fail(h, MCM_EINVAL, "bad flags (split weights: 16-bit modes, K % 64 == 0)");
-  if ((xs || os) && (prec != MCM_PREC_F16 || K % 64 || (os && (epi > EPI_GELU || N % 64))))
+  if (erf && epi != EPI_GELU) return fail(h, MCM_EINVAL, "bad flags (MCM_LINEAR_ACT_GELU: epilogue 1 only)");
+  if ((xs || os) && (prec != MCM_PREC_F16 || K % 64 || (os && (epi == EPI_RESID || N % 64))))
     return fail(h, MCM_EINVAL, "bad flags (split activations / outputs: fp16 mode, K % 64 == 0; outputs: epilogues 0 / 1, N % 64 == 0)");
   GemmArgs a{};
   a.x = x_dev; a.w = w_dev; a.bias = bias_dev; a.out = y_dev; a.resid = resid_dev;
   a.M = M; a.N = N; a.K = split ? 2 * K : K; a.ldx = xs ? 2 * K : K; a.ldo = os ? 2 * N : N; a.ksplit = split ? 1 : 0;
   a.xsplit = xs ? 1 : 0;
-  if (os) epi = epi == EPI_STORE ? EPI_STORE_X2 : EPI_GELU_X2;
+  if (os) epi = epi == EPI_STORE ? EPI_STORE_X2 : erf ? EPI_GELU_ERF_X2 : EPI_GELU_X2;
+  else if (erf) epi = EPI_GELU_ERF;
   a.sat = h->sat_on ? h->sat_dev : nullptr;
   HIP_TRY(h, launch_gemm(prec, epi, a, (hipStream_t)stream));
   return MCM_OK;
@@ -1411,6 +1423,23 @@ int mcm_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out
 }
 
 #ifdef MCM_HARNESS  // libmcm_hip_harness.so only: process-wide A/B switches for tests and tools
+// The MLP activations as the GEMM epilogues compute them (common.hpp), element-wise on a device array: the test that sweeps
+// every fp32 bit pattern through gelu_erf.  act: 0 quick_gelu, 1 quick_gelu_fast, 2 gelu_erf.
+__global__ void act_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n, int act) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    y[i] = act == 2 ? gelu_erf(x[i]) : act == 1 ? quick_gelu_fast(x[i]) : quick_gelu(x[i]);
+}
+int mcm_debug_op_act(mcm_handle* h, int32_t act, const float* x_dev, float* y_dev, int64_t n, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (act < 0 || act > 2 || !x_dev || !y_dev || n <= 0) return fail(h, MCM_EINVAL, "act 0 ... 2, n > 0, device pointers");
+  const size_t blocks = ((size_t)n + 255) / 256;
+  hipLaunchKernelGGL(act_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, x_dev, y_dev,
+                     (size_t)n, (int)act);
+  HIP_TRY(h, hipGetLastError());
+  return MCM_OK;
+}
+
 int mcm_debug_attention_variant(int32_t variant) {
   if (variant != 0 && variant != 1 && variant != 10 && variant != 11 && variant != 21 && variant != 36) return MCM_EINVAL;
   attention_set_variant(variant);

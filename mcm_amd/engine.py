@@ -92,6 +92,7 @@ def load_library(harness: bool = False):
     L.mcm_score_x2.argtypes = [vp, vp, i32, i32, vp, i32, f32, i32, vp, vp]
     if harness:
         L.mcm_debug_gemm_variant.argtypes = [i32]
+        L.mcm_debug_op_act.argtypes = [vp, i32, vp, vp, ctypes.c_int64, vp]
         L.mcm_debug_attention_variant.argtypes = [i32]
         L.mcm_debug_attn_spin_budget.argtypes = [ctypes.c_int64]
         L.mcm_debug_clear_faults.argtypes = [vp]
@@ -170,7 +171,8 @@ HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant",
                         "mcm_debug_persistent_grid", "mcm_debug_op_attention", "mcm_debug_attn_spin_budget",
                         "mcm_debug_clear_faults", "mcm_debug_ln_cluster", "mcm_debug_ln_cluster_spin",
                         "mcm_debug_ln_cluster_deferred", "mcm_debug_ln_row", "mcm_debug_op_attention_split",
-                        "mcm_debug_vision_front", "mcm_debug_op_pool_project", "mcm_debug_op_text_embed"]
+                        "mcm_debug_vision_front", "mcm_debug_op_pool_project", "mcm_debug_op_text_embed",
+                        "mcm_debug_op_act"]
 
 
 def _stream_ptr():

@@ -12,7 +12,11 @@ Schema source: transformers modeling_clip.py:138-159, 221-230, 280-296, 338-344,
 """
 from __future__ import annotations
 
+import json
+import logging
+import os
 import zlib
+from dataclasses import replace
 from typing import Dict, Tuple
 
 import numpy as np
@@ -152,9 +156,61 @@ def inject_outlier_channels(sd: Dict[str, np.ndarray], geo: ClipGeometry, *, cha
     return out, ch
 
 
+def _shape_of(geo: ClipGeometry):
+    """`geo` without its name and activations: two geometries with the same value are one model shape."""
+    return replace(geo, name="", v_hidden_act="", t_hidden_act="")
+
+
+def checkpoint_config_path(path: str):
+    """The HF `config.json` that belongs to a checkpoint: inside `path` when it is a directory, else beside the file.
+    None when there is none."""
+    d = path if os.path.isdir(path) else os.path.dirname(os.path.abspath(path))
+    p = os.path.join(d, "config.json")
+    return p if os.path.isfile(p) else None
+
+
+def check_hidden_act(path: str, geo: ClipGeometry) -> None:
+    """The guard against the silent failure of a checkpoint family mix-up.  An OpenAI and an OpenCLIP-trained checkpoint of
+    one geometry have the same tensor names and shapes and differ in `hidden_act` only (QuickGELU against the exact GELU),
+    which no tensor records: loaded under the wrong `--CLIP_ckpt` the model runs, and every score is plausible and wrong.
+    When the checkpoint's `config.json` is there, its `vision_config.hidden_act` / `text_config.hidden_act` must be the
+    geometry's; ValueError names both and the `--CLIP_ckpt` that matches.  Without a `config.json` nothing can be checked:
+    one log line says which activation is assumed — a warning when a geometry of the same shape with the other activation
+    exists (the mix-up is possible), else at info level."""
+    from .config import CHECKPOINTS, TEST_GEOMETRIES
+
+    log = logging.getLogger("mcm_amd")
+    cfg_path = checkpoint_config_path(path)
+    want = (geo.v_hidden_act, geo.t_hidden_act)
+    twins = [n for n, g in {**CHECKPOINTS, **TEST_GEOMETRIES}.items()
+             if _shape_of(g) == _shape_of(geo) and (g.v_hidden_act, g.t_hidden_act) != want]
+    if cfg_path is None:
+        log.log(logging.WARNING if twins else logging.INFO,
+                f"no config.json beside {path}: assuming hidden_act vision={want[0]} / text={want[1]} ({geo.name}); an "
+                f"OpenAI checkpoint has quick_gelu, an OpenCLIP-trained one gelu, and the tensors cannot tell")
+        return
+    with open(cfg_path) as f:
+        cfg = json.load(f)
+    # HF writes the activation into both sub-configs; a sub-config that leaves it out has CLIP*Config's default
+    got = tuple((cfg.get(k) or {}).get("hidden_act", "quick_gelu") for k in ("vision_config", "text_config"))
+    if got == want:
+        return
+    match = [n for n, g in CHECKPOINTS.items() if _shape_of(g) == _shape_of(geo) and (g.v_hidden_act, g.t_hidden_act) == got]
+    hint = f"--CLIP_ckpt {match[0]} matches it" if match else "no --CLIP_ckpt of this geometry has that pair"
+    raise ValueError(f"{cfg_path}: the checkpoint's hidden_act is vision={got[0]} / text={got[1]}, but {geo.name} runs "
+                     f"vision={want[0]} / text={want[1]}; {hint}")
+
+
 def load_state_dict_file(path: str, geo: ClipGeometry) -> Dict[str, np.ndarray]:
-    """Read a real checkpoint (`.safetensors` or torch state_dict) by HF names
-    (replaces CLIPModel.from_pretrained, reference utils/train_eval_util.py:23)."""
+    """Read a real checkpoint (`.safetensors` or torch state_dict; or a directory that holds `model.safetensors` /
+    `pytorch_model.bin`) by HF names (replaces CLIPModel.from_pretrained, reference utils/train_eval_util.py:23).  The
+    checkpoint's `config.json`, when present, must name the geometry's activations (check_hidden_act)."""
+    if os.path.isdir(path):
+        found = [fn for fn in ("model.safetensors", "pytorch_model.bin") if os.path.isfile(os.path.join(path, fn))]
+        if not found:
+            raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin")
+        path = os.path.join(path, found[0])
+    check_hidden_act(path, geo)
     if path.endswith(".safetensors"):
         from safetensors.numpy import load_file
 
