@@ -49,7 +49,9 @@ def process_args(argv=None):
     p.add_argument("--CLIP_ckpt", type=str, default="ViT-B/16",
                    choices=["ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336px",
                             # OpenCLIP-trained (LAION-2B) checkpoints in HF layout: the exact GELU in both towers
-                            "ViT-B/32-laion2b", "ViT-B/16-laion2b", "ViT-L/14-laion2b"],
+                            "ViT-B/32-laion2b", "ViT-B/16-laion2b", "ViT-L/14-laion2b",
+                            # ... and OpenCLIP's ViT-H/14: a 1280-wide vision tower with 80-wide heads
+                            "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
                    choices=["MCM", "energy", "max-logit", "entropy", "var", "maha"], help="score options")

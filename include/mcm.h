@@ -100,8 +100,9 @@ typedef struct mcm_config {
   /* vision tower (modeling_clip.py:138-218, 594-656) */
   int32_t image_size;       /* 224                                                    */
   int32_t patch_size;       /* 16 (B/16), 32 (B/32), 14 (L/14)                        */
-  int32_t v_width;          /* 768 / 1024                                             */
-  int32_t v_heads;          /* 12 / 16  (head_dim = width / heads must be 64)         */
+  int32_t v_width;          /* 768 / 1024 / 1280 (ViT-H/14)                           */
+  int32_t v_heads;          /* 12 / 16  (head_dim = width / heads: 64, or 80 in the   */
+                            /* vision tower only — ViT-H/14; the text tower: 64)      */
   int32_t v_layers;         /* 12 / 24                                                */
   int32_t v_mlp;            /* 3072 / 4096                                            */
   /* text tower (modeling_clip.py:221-256, 494-586) */
@@ -391,13 +392,17 @@ int mcm_op_layernorm(mcm_handle* h, int32_t prec, const float* x_dev, const floa
                      const float* beta_dev, void* y_dev, int32_t M, int32_t D, float eps,
                      int32_t out_f32, void* stream);
 /* The split-activation arm's LayerNorm and attention (fp16): y [M, 2D] / out [rows, 2 heads 64] are split images (per 64
- * columns hi[64] then lo[64]); mcm_op_attention_split reads qkv as a split image [rows, 6 heads 64]. */
+ * columns hi[64] then lo[64]); mcm_op_attention_split reads qkv as a split image [rows, 6 heads 64].  head_dim 64; the
+ * model's vision tower also runs head_dim 80 (ViT-H/14), which the operator level reaches through the harness library's
+ * mcm_debug_op_attention_split_hd. */
 int mcm_op_layernorm_split(mcm_handle* h, const float* x_dev, const float* gamma_dev, const float* beta_dev,
                            void* y_dev, int32_t M, int32_t D, float eps, void* stream);
 int mcm_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                            int32_t heads, void* stream);
 /* Multi-head SDPA (modeling_clip.py:259-277,313-331): qkv [nseq*seq_len, 3*heads*64]
- * packed as [q | k | v], head_dim 64, scale 0.125; causal != 0 for the text tower.
+ * packed as [q | k | v], head_dim 64, scale 0.125; causal != 0 for the text tower.  (This entry point means head_dim 64;
+ * the model's vision tower also runs head_dim 80, scale 80^-0.5 — ViT-H/14, a streaming family of its own at every length —
+ * which the operator level reaches through the harness library's mcm_debug_op_attention_hd.)
  * out [nseq*seq_len, heads*64].  Two routes, chosen by length:
  *   seq_len ≤ 288 (18 key tiles of 16): K and V of a head held whole in LDS (the B/32, B/16 and L/14 towers, causal text);
  *   seq_len 289 ... 1025, bidirectional only: K and V streamed through LDS in 64-key tiles with an online softmax (every mode,
@@ -461,6 +466,15 @@ int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, voi
  * direction. */
 int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                                  int32_t heads, int32_t qrows, int32_t reverse, void* stream);
+/* The two above with the head width as an argument.  head_dim 64: their routes.  head_dim 80: the streaming family of
+ * ViT-H/14's vision tower — qkv [rows, 3 heads 80], head h at column 80 h of q, k and v, scale 80^-0.5, bidirectional only
+ * (causal != 0 is refused), seq_len <= 1025; the split form's images are "per 64 columns hi[64] then lo[64]" over the whole
+ * heads x 80 row (column c at (c / 64) 128 + c % 64, lo 64 further): a head straddles blocks.  Any other head_dim is refused.
+ * A refused call launches nothing. */
+int mcm_debug_op_attention_hd(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                              int32_t heads, int32_t head_dim, int32_t causal, int32_t qrows, int32_t reverse, void* stream);
+int mcm_debug_op_attention_split_hd(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                                    int32_t heads, int32_t head_dim, int32_t qrows, int32_t reverse, void* stream);
 /* The front of the vision tower as mcm_encode_image* run it (the same function, the handle's own weights and workspace), stopped
  * at `stage`: 0 = behind the patch-embedding GEMM, 1 = behind the fused CLS row + pre_layrnorm + layer 0 layer_norm1 pass.  The
  * fp32 residual rows [B * tokens, v_width] are copied to resid_out_dev (at stage 0 the CLS rows are whatever the workspace held);
@@ -472,7 +486,7 @@ int mcm_debug_vision_front(mcm_handle* h, const void* pixels_dev, int32_t pixel_
                            int32_t poison, float* resid_out_dev, void* ln_out_dev, void* stream);
 /* The pooling kernel of both towers on the caller's buffers: row i of out [n, P] = normalise?(LayerNorm(x[row]) proj^T) with
  * row = row_idx_host[i], or i * row_stride when row_idx_host is NULL; x [x_rows, D] fp32, proj [P, D] fp32.  The indices are
- * host memory and are checked against x_rows.  MCM_EINVAL for D > 1024, D % 4 != 0, P > 1024 or a row outside x.
+ * host memory and are checked against x_rows.  MCM_EINVAL for D > 1280, D % 4 != 0 (past 1024: D % 64 != 0), P > 1024 or a row outside x.
  * Synchronises the stream. */
 int mcm_debug_op_pool_project(mcm_handle* h, const float* x_dev, int64_t x_rows, const int32_t* row_idx_host, int32_t row_stride,
                               int32_t n, int32_t D, const float* gamma_dev, const float* beta_dev, float eps,

@@ -4,6 +4,6 @@ Host side of the hot path `get_ood_scores_clip` (reference utils/detection_util.
 Python over the C ABI of libmcm_hip.so (include/mcm.h).  There is no CPU fallback: the
 engine raises if the HIP library is missing.
 """
-from .config import CHECKPOINTS, TEST_GEOMETRIES, ClipGeometry, geometry  # noqa: F401
+from .config import CHECKPOINTS, TEST_GEOMETRIES, WIDE_HEAD_CHECKPOINTS, ClipGeometry, all_checkpoints, geometry  # noqa: F401
 
-__all__ = ["CHECKPOINTS", "TEST_GEOMETRIES", "ClipGeometry", "geometry"]
+__all__ = ["CHECKPOINTS", "TEST_GEOMETRIES", "WIDE_HEAD_CHECKPOINTS", "ClipGeometry", "all_checkpoints", "geometry"]

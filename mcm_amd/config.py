@@ -184,6 +184,18 @@ CHECKPOINTS = {
 for _name in ("ViT-B/32", "ViT-B/16", "ViT-L/14"):
     CHECKPOINTS[_name + "-laion2b"] = replace(CHECKPOINTS[_name], name=_name + "-laion2b", v_hidden_act="gelu", t_hidden_act="gelu")
 del _name
+# ... and the one people reach for when they want a stronger zero-shot detector than L/14: OpenCLIP's ViT-H-14 (vision width
+# 1280, head_width 80 — NOT 64: the head_dim-80 attention family, DESIGN.md 4.8 —, mlp_ratio 4, 32 layers; text 1024 wide,
+# 16 heads of 64, 24 layers; embed_dim 1024).  UNVERIFIED like the hub ids below: written from memory of OpenCLIP's model
+# definition, no hub was reachable to check the dimensions against.
+# A registry of its own, NOT an entry of CHECKPOINTS: tests/test_gelu_geometry.py pins list(CHECKPOINTS)[4:] to the three LAION
+# twins of the OpenAI names, and an existing test does not change for a new checkpoint.  So CHECKPOINTS stays the seven names whose
+# towers are 64 wide per head; geometry(), the CLI and the config.json guard look in both registries.  Code that wants EVERY
+# checkpoint iterates all_checkpoints(), never CHECKPOINTS alone (a loop over CHECKPOINTS silently misses this one).
+WIDE_HEAD_CHECKPOINTS = {}
+WIDE_HEAD_CHECKPOINTS["ViT-H/14-laion2b"] = ClipGeometry("ViT-H/14-laion2b", patch_size=14, v_width=1280, v_heads=16, v_layers=32,
+                                               v_mlp=5120, t_width=1024, t_heads=16, t_layers=24, t_mlp=4096, proj_dim=1024,
+                                               v_hidden_act="gelu", t_hidden_act="gelu")
 HUB_IDS = {
     "ViT-B/32": "openai/clip-vit-base-patch32",
     "ViT-B/16": "openai/clip-vit-base-patch16",
@@ -194,10 +206,11 @@ HUB_IDS = {
     "ViT-B/32-laion2b": "laion/CLIP-ViT-B-32-laion2B-s34B-b79K",
     "ViT-B/16-laion2b": "laion/CLIP-ViT-B-16-laion2B-s34B-b88K",
     "ViT-L/14-laion2b": "laion/CLIP-ViT-L-14-laion2B-s32B-b82K",
+    "ViT-H/14-laion2b": "laion/CLIP-ViT-H-14-laion2B-s32B-b79K",
 }
 
-# Reduced geometries for fast parity tests: full-width heads (head_dim 64) and every code
-# path of the real towers, few layers / small images so the CPU oracle runs in seconds.
+# Reduced geometries for fast parity tests: full-width heads (head_dim 64; 80 in the vision tower of the H14 pair) and every
+# code path of the real towers, few layers / small images so the CPU oracle runs in seconds.
 TEST_GEOMETRIES = {
     # 2-layer full-width B/16: per-op / per-layer intermediates
     "B16-2L": replace(CHECKPOINTS["ViT-B/16"], name="B16-2L", v_layers=2, t_layers=2),
@@ -209,11 +222,23 @@ TEST_GEOMETRIES = {
 # the same two with the exact GELU in both towers (the OpenCLIP-trained family)
 TEST_GEOMETRIES["tiny-gelu"] = replace(TEST_GEOMETRIES["tiny"], name="tiny-gelu", v_hidden_act="gelu", t_hidden_act="gelu")
 TEST_GEOMETRIES["B16-2L-gelu"] = replace(TEST_GEOMETRIES["B16-2L"], name="B16-2L-gelu", v_hidden_act="gelu", t_hidden_act="gelu")
+# the H/14 towers (1280 wide, head_dim 80 in the vision tower) with 2 + 2 layers; "-quick" with QuickGELU, the only activation
+# the C oracle computes
+TEST_GEOMETRIES["H14-2L"] = replace(WIDE_HEAD_CHECKPOINTS["ViT-H/14-laion2b"], name="H14-2L", v_layers=2, t_layers=2)
+TEST_GEOMETRIES["H14-2L-quick"] = replace(TEST_GEOMETRIES["H14-2L"], name="H14-2L-quick", v_hidden_act="quick_gelu",
+                                          t_hidden_act="quick_gelu")
+
+
+def all_checkpoints() -> dict:
+    """Every checkpoint name -> geometry: CHECKPOINTS, then WIDE_HEAD_CHECKPOINTS."""
+    return {**CHECKPOINTS, **WIDE_HEAD_CHECKPOINTS}
 
 
 def geometry(name: str) -> ClipGeometry:
     if name in CHECKPOINTS:
         return CHECKPOINTS[name]
+    if name in WIDE_HEAD_CHECKPOINTS:
+        return WIDE_HEAD_CHECKPOINTS[name]
     if name in TEST_GEOMETRIES:
         return TEST_GEOMETRIES[name]
     raise KeyError(f"unknown CLIP geometry {name!r}")

@@ -1,5 +1,6 @@
 // attention.hip — fused multi-head SDPA for short, fixed sequences (197 / 257 / 50 vision
-// tokens, <=77 text tokens), head_dim 64, scale 0.125, fp32 softmax.
+// tokens, <=77 text tokens), head_dim 64, scale 0.125, fp32 softmax.  (head_dim 80, ViT-H/14's vision tower: the
+// streaming family attn_hd80_kernel / attn_hd80_f32_kernel below the long-sequence kernels.)
 //
 // Replaces CLIPAttention's SDPA (HF modeling_clip.py:259-277 eager definition, :313-331;
 // causal for the text tower :543-556).  One workgroup per (sequence, head): the whole K
@@ -1386,6 +1387,385 @@ hipError_t launch_long(const void* qkv, void* out, int nseq, int L, int heads, i
 }
 
 
+// ---- head_dim 80 (ViT-H/14: 1280 wide, 16 heads): the streaming family at 160-byte head rows -----------------------------
+// Siblings of attn_long_kernel / attn_long_f32_kernel, at every length 1 ... LONG_MAX_L (no LDS-resident form: K + V of a head
+// at 257 tokens are 87 KB in 16 bits, 174 KB split or fp32).  Same grid, same 64-key double-buffered tiles, same textbook
+// online-softmax order; what differs:
+//   * scale 80^-0.5 (not a power of two), folded with log2 e into ONE fp32 constant;
+//   * S^T = K Q^T over 80 dims = THREE 16x16x32 steps, the third over a zero-padded tail: lane groups g = 0, 1 carry dims
+//     64 - 79, the Q operand of groups 2, 3 is zero (their K operand re-reads chunks 8 / 9: finite data times zero).  Not two
+//     32-deep steps + one v_mfma_f32_16x16x16: mixing the two shapes in one accumulator chain gave wrong blocks when
+//     attn_tr_kernel was brought up (see mfma_keep above), and a separate chain would cost an extra add per score;
+//   * O = five 16-dim blocks: blocks 0 - 3 leave through the v_permlane16_swap pairs (16-byte stores), block 4 through an
+//     8-byte store of its own;
+//   * LDS images are LINEAR [key][160 B], K and V alike: with the lane groups ds_read_b128 is serviced in ({0-3, 12-15, 20-27},
+//     {4-11, 16-19, 28-31}, ...) the 16 rows x 4 chunks of a K fragment read fall on 16 distinct 16-byte bank groups per
+//     cycle at a 160-byte stride (10 r + c mod 16), and the 8 keys x 32 B of a transpose read on 8 distinct 32-byte groups
+//     (5 k + s mod 8): no swizzle.  A 64-key image is 640 16-byte chunks = 10 DMA pieces; chunk P of an image is (row P / 10,
+//     chunk P % 10);
+//   * split images (X2): "per 64 columns hi[64] then lo[64]" over the whole 1280-column row, so a head straddles blocks; an
+//     8-column chunk never does, and every 16-byte access computes split_col of its own first column.
+// Static LDS: 16-bit 2 stages x (K + V) x 10 KiB = 40960 B, X2 81920 B.  No inter-workgroup waits, no fault word.
+constexpr int H80 = 80;                        // head_dim
+constexpr int H80_IMG = LONG_KT * H80 * 2;     // bytes of one 16-bit K or V image of a tile
+constexpr float H80_SCALE = 0.11180339887498949f;                 // 80^-0.5
+constexpr float H80_SC = (float)(0.11180339887498949 * 1.4426950408889634);   // 80^-0.5 * log2(e), rounded once
+
+template <int PREC, bool X2>
+__global__ __launch_bounds__(LONG_NW * 64, 2) void attn_hd80_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
+                                                                    int L, int heads, int qrows, int nchunk, int rev) {
+  static_assert(!X2 || PREC == MCM_PREC_F16, "split activations: fp16");
+  enter_precision_mode<PREC>();
+  constexpr int IMG = H80_IMG;                    // 10240
+  constexpr int PARTS = X2 ? 2 : 1;               // hi, (X2) lo
+  constexpr int STAGE = 2 * PARTS * IMG;          // [part][K, V][IMG]
+  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];   // static: the code object states the footprint
+  constexpr int PPI = IMG / 1024;                 // 10 DMA pieces per image
+  constexpr int NP = 2 * PARTS * PPI;             // pieces per tile: 20 / 40, dealt round-robin to the waves
+  constexpr int NPW = (NP + LONG_NW - 1) / LONG_NW;
+  constexpr uint32_t ONE2 = PREC == MCM_PREC_F16 ? 0x3c003c00u : 0x3f803f80u;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bid = (rev & 1) ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int sh = bid / nchunk, chunk = bid - sh * nchunk;
+  const int seq = sh / heads, h = sh - seq * heads;
+  const int D = heads * H80;
+  const size_t rs = X2 ? (size_t)6 * D : (size_t)3 * D;     // qkv row stride (elements)
+  const size_t KO = X2 ? (size_t)2 * D : (size_t)D, VO = 2 * KO;
+  const uint16_t* base = qkv + (size_t)seq * L * rs;        // row 0 of the sequence, column 0 of q
+  // element offset of dim d (a multiple of 4) of this head inside a q, k, v or output row; X2: the lo element is 64 further
+  auto col = [&](int d) -> size_t { return X2 ? split_col(h * H80 + d) : (size_t)(h * H80 + d); };
+  const int fr = lane & 15, g = lane >> 4;
+  const int qb = chunk * LONG_NW + wave;
+  const bool active = qb < (qrows + 15) / 16;     // wave-uniform: an idle wave still loads its share of every tile
+  const int q = qb * 16 + fr;
+  const int ntile = (L + LONG_KT - 1) / LONG_KT;
+
+  auto issue_tile = [&](int j) {
+    const uint32_t sb = lds_addr(smem) + (uint32_t)((j & 1) * STAGE);
+    const int k0 = j * LONG_KT;
+#pragma unroll
+    for (int i = 0; i < NPW; ++i) {
+      const int piece = wave + LONG_NW * i;                        // [part][K, V][10 pieces]
+      if (piece < NP) {
+        const int img = piece / PPI, blk = piece - img * PPI, part = img >> 1, kind = img & 1;
+        const int P = blk * 64 + lane, row = P / 10, c = P - row * 10;   // linear image: 10 chunks per key row
+        const uint16_t* src = base + (size_t)min(k0 + row, L - 1) * rs + (kind ? VO : KO) + col(c * 8) + part * 64;
+        glds16(src, sb + (uint32_t)(img * IMG + blk * 1024));
+      }
+    }
+  };
+
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+  uint4 q0, q1, q2, ql0 = z4, ql1 = z4, ql2 = z4;
+  {
+    const uint16_t* qp = base + (size_t)min(q, L - 1) * rs;
+    const size_t c0 = col(g * 8), c1 = col(32 + g * 8), c2 = col(64 + (g & 1) * 8);
+    q0 = *(const uint4*)(qp + c0);
+    q1 = *(const uint4*)(qp + c1);
+    q2 = *(const uint4*)(qp + c2);
+    if constexpr (X2) {
+      ql0 = *(const uint4*)(qp + c0 + 64);
+      ql1 = *(const uint4*)(qp + c1 + 64);
+      ql2 = *(const uint4*)(qp + c2 + 64);
+    }
+    if (g >= 2) { q2 = z4; ql2 = z4; }   // the zero-padded tail of the third 32-deep step
+  }
+  issue_tile(0);
+  // Q is waited for here, once (attn_long_kernel: left to hipcc, the wait lands in the tile loop and drains the next tile's DMA)
+  asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, q0)), "v"(__builtin_bit_cast(u32x4_t, q1)), "v"(__builtin_bit_cast(u32x4_t, q2)),
+               "v"(__builtin_bit_cast(u32x4_t, ql0)), "v"(__builtin_bit_cast(u32x4_t, ql1)), "v"(__builtin_bit_cast(u32x4_t, ql2)));
+
+  const int koff = fr * (H80 * 2) + g * 16;                         // key row fr of a 16-key subtile, chunk g of a 32-dim step
+  const int koff2 = fr * (H80 * 2) + 128 + (g & 1) * 16;            // chunks 8 / 9
+  // V^T fragment of subtile t, dims [16 dt, 16 dt + 16): this lane reads 4 dims of key 16 t + 4 g + fr / 4
+  const int voff = IMG + (4 * g + (fr >> 2)) * (H80 * 2) + (fr & 3) * 8;
+  constexpr int TS = 16 * H80 * 2;                                  // bytes of a 16-key subtile
+  const f32x4_t zero = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  f32x4_t lacc = zero;
+  f32x4_t o[5] = {zero, zero, zero, zero, zero};
+  float m = -INFINITY;
+
+  for (int j = 0; j < ntile; ++j) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile j have landed ...
+    __syncthreads();                                    // ... and everybody's; every wave is done with tile j - 1's stage
+    if (j + 1 < ntile) issue_tile(j + 1);
+    if (!active) continue;
+    const char* Ks = smem + (j & 1) * STAGE;
+    f32x4_t s[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const char* kp = Ks + t * TS;
+      const uint4 k0 = *(const uint4*)(kp + koff), k1 = *(const uint4*)(kp + koff + 64), k2 = *(const uint4*)(kp + koff2);
+      if constexpr (X2) {  // the cross terms first (small), then the leading one: one fp32 accumulator chain
+        const uint4 kl0 = *(const uint4*)(kp + 2 * IMG + koff), kl1 = *(const uint4*)(kp + 2 * IMG + koff + 64);
+        const uint4 kl2 = *(const uint4*)(kp + 2 * IMG + koff2);
+        s[t] = mfma_keep<PREC>(kl0, q0, zero);
+        s[t] = mfma_keep<PREC>(kl1, q1, s[t]);
+        s[t] = mfma_keep<PREC>(kl2, q2, s[t]);
+        s[t] = mfma_keep<PREC>(k0, ql0, s[t]);
+        s[t] = mfma_keep<PREC>(k1, ql1, s[t]);
+        s[t] = mfma_keep<PREC>(k2, ql2, s[t]);
+        s[t] = mfma_keep<PREC>(k0, q0, s[t]);
+        s[t] = mfma_keep<PREC>(k1, q1, s[t]);
+        s[t] = mfma_keep<PREC>(k2, q2, s[t]);
+      } else {
+        s[t] = mfma_keep<PREC>(k0, q0, zero);
+        s[t] = mfma_keep<PREC>(k1, q1, s[t]);
+        s[t] = mfma_keep<PREC>(k2, q2, s[t]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    float mt = -INFINITY;
+    const bool full = j * LONG_KT + LONG_KT <= L;      // uniform: only the last tile can hold keys past L
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (!full) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[t][r] = (j * LONG_KT + t * 16 + g * 4 + r < L) ? s[t][r] : -INFINITY;
+      }
+      mt = fmaxf(fmaxf(fmaxf(fmaxf(mt, s[t][0]), s[t][1]), s[t][2]), s[t][3]);
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float mn = fmaxf(m, mt);                     // finite: every tile holds at least one valid key
+    const float a = __builtin_amdgcn_exp2f((m - mn) * H80_SC);   // exp2(-inf) = 0 on the first tile
+    m = mn;
+    lacc *= a;
+#pragma unroll
+    for (int dt = 0; dt < 5; ++dt) o[dt] *= a;
+    const float msc = X2 ? mn * H80_SC - 12.0f : mn * H80_SC;  // X2: P scaled by 2^12 (attn_tr_kernel's header); cancels in O / l
+    uint2 pt[4], pl[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float e[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(fmaf(s[t][r], H80_SC, -msc));
+      if constexpr (X2) {
+        split2<PREC>(e[0], e[1], pt[t].x, pl[t].x);
+        split2<PREC>(e[2], e[3], pt[t].y, pl[t].y);
+      } else {
+        pt[t] = make_uint2(pack2<PREC>(e[0], e[1]), pack2<PREC>(e[2], e[3]));
+        pl[t] = make_uint2(0u, 0u);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {  // two 32-key steps per tile: six independent accumulator chains
+      const uint4 pu = make_uint4(pt[2 * u].x, pt[2 * u].y, pt[2 * u + 1].x, pt[2 * u + 1].y);
+      const uint4 plu = make_uint4(pl[2 * u].x, pl[2 * u].y, pl[2 * u + 1].x, pl[2 * u + 1].y);
+      if constexpr (X2) lacc = mfma_keep<PREC>(make_uint4(ONE2, ONE2, ONE2, ONE2), plu, lacc);
+      lacc = mfma_keep<PREC>(make_uint4(ONE2, ONE2, ONE2, ONE2), pu, lacc);
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        const char* vp = Ks + voff + dt * 32;
+        const uint2 lo = tr_read16(vp + (2 * u) * TS), hi = tr_read16(vp + (2 * u + 1) * TS);
+        if constexpr (X2) {  // V_lo P_hi and V_hi P_lo first, then the leading term
+          const uint2 llo = tr_read16(vp + 2 * IMG + (2 * u) * TS), lhi = tr_read16(vp + 2 * IMG + (2 * u + 1) * TS);
+          o[dt] = mfma_keep<PREC>(make_uint4(llo.x, llo.y, lhi.x, lhi.y), pu, o[dt]);
+          o[dt] = mfma_keep<PREC>(make_uint4(lo.x, lo.y, hi.x, hi.y), plu, o[dt]);
+        }
+        o[dt] = mfma_keep<PREC>(make_uint4(lo.x, lo.y, hi.x, hi.y), pu, o[dt]);
+      }
+    }
+  }
+  if (!active) return;
+  const float rl = 1.0f / lacc[0];
+  uint32_t pk[5][2], pkl[5][2];
+#pragma unroll
+  for (int dt = 0; dt < 5; ++dt) {
+    if constexpr (X2) {
+      split2<PREC>(o[dt][0] * rl, o[dt][1] * rl, pk[dt][0], pkl[dt][0]);
+      split2<PREC>(o[dt][2] * rl, o[dt][3] * rl, pk[dt][1], pkl[dt][1]);
+    } else {
+      pk[dt][0] = pack2<PREC>(o[dt][0] * rl, o[dt][1] * rl);
+      pk[dt][1] = pack2<PREC>(o[dt][2] * rl, o[dt][3] * rl);
+      pkl[dt][0] = pkl[dt][1] = 0u;
+    }
+  }
+  uint4 wide[2], widel[2];
+#pragma unroll
+  for (int pr = 0; pr < 2; ++pr) {  // (attn_tr_kernel's store: a lane ends up with 8 consecutive dims of one 16-dim block)
+    const auto w0 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][0], pk[2 * pr + 1][0], false, false);
+    const auto w1 = __builtin_amdgcn_permlane16_swap(pk[2 * pr][1], pk[2 * pr + 1][1], false, false);
+    wide[pr] = make_uint4(w0[0], w1[0], w0[1], w1[1]);
+    if constexpr (X2) {
+      const auto l0 = __builtin_amdgcn_permlane16_swap(pkl[2 * pr][0], pkl[2 * pr + 1][0], false, false);
+      const auto l1 = __builtin_amdgcn_permlane16_swap(pkl[2 * pr][1], pkl[2 * pr + 1][1], false, false);
+      widel[pr] = make_uint4(l0[0], l1[0], l0[1], l1[1]);
+    }
+  }
+  // (like attn_long_kernel, its 64-wide sibling, an active block stores all of its rows q < L, so qrows = 1 also writes rows
+  // 1 .. 15 — correct values nobody reads; the fp32 pair, attn_long_f32_kernel / attn_hd80_f32_kernel, stores q < qrows only)
+  if (q < L) {
+    uint16_t* orow = out + ((size_t)seq * L + q) * (X2 ? 2 : 1) * D;
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {  // blocks 0 - 3: 8 consecutive dims (one 16-byte chunk: never across a 64-column block)
+      uint16_t* dst = orow + col((2 * pr + (g & 1)) * 16 + (g & 2) * 4);
+      *(uint4*)dst = wide[pr];
+      if constexpr (X2) *(uint4*)(dst + 64) = widel[pr];
+    }
+    uint16_t* dst4 = orow + col(64 + g * 4);   // block 4 has no partner to swap with: the lane's own 4 dims, 8 bytes
+    *(uint2*)dst4 = make_uint2(pk[4][0], pk[4][1]);
+    if constexpr (X2) *(uint2*)(dst4 + 64) = make_uint2(pkl[4][0], pkl[4][1]);
+  }
+}
+
+// Exact fp32 form at head_dim 80: attn_long_f32_kernel's arithmetic and staging with 20 k-steps of v_mfma_f32_16x16x4_f32 per
+// 16-key subtile (the matrix pipe's k-slot g carries dims 20 g + j, j = 0 .. 19: a lane's operand values are 20 CONSECUTIVE
+// floats of its row, five 16-byte reads) and five output blocks.  K rows are padded to 88 floats (352 B = 22 x 16 B: the
+// ds_read_b128 lane groups fall on 16 distinct bank groups; 84 is 2-way there), V rows to 84 (336 B: the 4 x 16 dwords of a
+// PV fragment read fall on distinct banks; 88 is 2-way there).  Static LDS: 2 stages x 64 x (352 + 336) B = 88064 B, so ONE
+// workgroup per CU (two would need 172 KiB): the parity arm re-scores, it does not carry the throughput.
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 1) void attn_hd80_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L,
+                                                                   int heads, int qrows, int nchunk, int rev) {
+  constexpr int RSK = 88, RSV = 84, KIMG = LONG_KT * RSK, STG = LONG_KT * (RSK + RSV);   // floats
+  constexpr int NF4 = LONG_KT * (H80 / 4);                       // float4 of each image per tile: 1280
+  constexpr int NLD = (NF4 + NW * 64 - 1) / (NW * 64);           // per thread: 3 (the last round: half the workgroup)
+  __shared__ __attribute__((aligned(16))) float stage[2 * STG];   // [2][K image, V image]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bid = (rev & 1) ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int sh = bid / nchunk, chunk = bid - sh * nchunk;
+  const int seq = sh / heads, h = sh - seq * heads;
+  const int D = heads * H80;
+  const size_t rs = (size_t)3 * D;
+  const float* base = qkv + (size_t)seq * L * rs + h * H80;
+  const int fr = lane & 15, g = lane >> 4;
+  const int qb = chunk * NW + wave;
+  const bool active = qb < (qrows + 15) / 16;
+  const int q = qb * 16 + fr;
+  const int ntile = (L + LONG_KT - 1) / LONG_KT;
+
+  f32x4_t kr[NLD], vr[NLD];
+  auto fetch = [&](int j) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = threadIdx.x + i * NW * 64;
+      if (idx < NF4) {
+        const int row = idx / 20, c = (idx - row * 20) * 4;
+        const float* rp = base + (size_t)min(j * LONG_KT + row, L - 1) * rs + c;
+        kr[i] = *(const f32x4_t*)(rp + D);
+        vr[i] = *(const f32x4_t*)(rp + 2 * D);
+      }
+    }
+  };
+  auto stash = [&](int j) {
+    float* Ks = stage + (j & 1) * STG;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = threadIdx.x + i * NW * 64;
+      if (idx < NF4) {
+        const int row = idx / 20, c = (idx - row * 20) * 4;
+        *(f32x4_t*)(Ks + row * RSK + c) = kr[i];
+        *(f32x4_t*)(Ks + KIMG + row * RSV + c) = vr[i];
+      }
+    }
+  };
+  float qv[20];
+  {
+    const float* qp = base + (size_t)min(q, L - 1) * rs + 20 * g;
+#pragma unroll
+    for (int j4 = 0; j4 < 5; ++j4) {
+      const f32x4_t t = *(const f32x4_t*)(qp + 4 * j4);
+      qv[4 * j4] = t[0]; qv[4 * j4 + 1] = t[1]; qv[4 * j4 + 2] = t[2]; qv[4 * j4 + 3] = t[3];
+    }
+  }
+  fetch(0);
+  stash(0);
+#pragma unroll
+  for (int i = 0; i < 20; ++i) asm volatile("" : "+v"(qv[i]));   // Q waited for once, not inside the loop behind the prefetch
+  __syncthreads();
+  f32x4_t o[5];
+#pragma unroll
+  for (int dt = 0; dt < 5; ++dt) o[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, z = 0.f;
+  for (int j = 0; j < ntile; ++j) {
+    if (j + 1 < ntile) fetch(j + 1);
+    if (active) {
+      const float* Ks = stage + (j & 1) * STG;
+      const float* Vs = Ks + KIMG;
+      f32x4_t s[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const float* kp = Ks + (t * 16 + fr) * RSK + 20 * g;
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j4 = 0; j4 < 5; ++j4) {
+          const f32x4_t kk = *(const f32x4_t*)(kp + 4 * j4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kk[e], qv[4 * j4 + e], acc, 0, 0, 0);
+        }
+        s[t] = acc;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      float mt = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool ok = j * LONG_KT + t * 16 + g * 4 + r < L;
+          s[t][r] = ok ? s[t][r] * H80_SCALE : -INFINITY;
+          mt = fmaxf(mt, s[t][r]);
+        }
+      }
+      mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
+      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      const float mn = fmaxf(m, mt);
+      const float a = expf(m - mn);   // (-inf - mn: 0)
+      m = mn;
+      z *= a;
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) o[dt] *= a;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = expf(s[t][r] - mn);
+          s[t][r] = e;
+          z += e;
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float* vp = Vs + (t * 16 + 4 * g + r) * RSV + fr;
+#pragma unroll
+          for (int dt = 0; dt < 5; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[dt * 16], s[t][r], o[dt], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (j + 1 < ntile) stash(j + 1);   // the stage tile j - 1 used: every wave passed the previous barrier after reading it
+    __syncthreads();
+  }
+  z += __shfl_xor(z, 16, 64);
+  z += __shfl_xor(z, 32, 64);
+  if (active && q < L && q < qrows) {
+    const float rz = 1.0f / z;
+    float* orow = out + ((size_t)seq * L + q) * D + h * H80 + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < 5; ++dt) *(f32x4_t*)(orow + dt * 16) = o[dt] * rz;
+  }
+}
+
+// Grid: launch_long's — nseq x heads x query chunks of LONG_NW 16-query blocks.
+template <int PREC, bool X2>
+hipError_t launch_hd80(const void* qkv, void* out, int nseq, int L, int heads, int qrows, hipStream_t s, int rev) {
+  const int nqb = (qrows + 15) / 16, nchunk = (nqb + LONG_NW - 1) / LONG_NW;
+  const int64_t grid = (int64_t)nseq * heads * nchunk;
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if constexpr (PREC == MCM_PREC_F32)
+    hipLaunchKernelGGL((attn_hd80_f32_kernel<LONG_NW>), dim3((unsigned)grid), dim3(LONG_NW * 64), 0, s, (const float*)qkv,
+                       (float*)out, L, heads, qrows, nchunk, rev);
+  else
+    hipLaunchKernelGGL((attn_hd80_kernel<PREC, X2>), dim3((unsigned)grid), dim3(LONG_NW * 64), 0, s, (const uint16_t*)qkv,
+                       (uint16_t*)out, L, heads, qrows, nchunk, rev);
+  return hipGetLastError();
+}
+
+
 // Waves per workgroup.  The q-blocks of a sequence are dealt round-robin to the waves, so the slowest wave has
 // ceil(q-blocks / waves) of them.  Measured at B/16 batch 512 / L/14 batch 256 (tools/attn_probe.py — removed in round 6 —, same
 // box, old kernel 215 / 295 us): 4 waves (4-3-3-3 blocks) 164 - 167 / 183 - 186 us, 5 - 6 waves 171 - 178, 7 waves
@@ -1429,10 +1809,24 @@ void attention_set_variant(int v) { g_attn_variant = v; }
 void attention_set_spin_budget(unsigned int polls) { g_ps_spin_budget = polls; }
 #endif
 
-hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads,
+hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads, int head_dim,
                             bool causal, int qrows, hipStream_t s, bool reverse, int hm, bool split, unsigned int* fault) {
   if (nseq <= 0 || L <= 0 || heads <= 0) return hipErrorInvalidValue;
+  if (head_dim != 64 && head_dim != H80) return hipErrorInvalidValue;
   if (qrows <= 0 || qrows > L) qrows = L;
+  // head_dim 80 (ViT-H/14's vision tower): the streaming family at every length; bidirectional, row-major qkv only
+  if (head_dim == H80) {
+    if (causal || hm || L > LONG_MAX_L) return hipErrorInvalidValue;
+    const int rv = reverse ? 1 : 0;
+    if (split) {  // (a split row is whole 64-column blocks: heads a multiple of 4)
+      if (prec != MCM_PREC_F16 || (heads * H80) % 64) return hipErrorInvalidValue;
+      return launch_hd80<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, rv);
+    }
+    if (prec == MCM_PREC_F16) return launch_hd80<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, rv);
+    if (prec == MCM_PREC_BF16) return launch_hd80<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, rv);
+    if (prec == MCM_PREC_F32) return launch_hd80<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, rv);
+    return hipErrorInvalidValue;
+  }
   // Bidirectional problems past 18 key tiles (L > 288): the streaming kernels (K / V through LDS, online softmax), every mode.
   // Everything at L <= 288, and causal attention at any length, keeps the kernels below.
   if (!causal && (L + 15) / 16 > 18) {

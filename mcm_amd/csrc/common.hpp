@@ -385,7 +385,8 @@ hipError_t launch_layernorm_pre(int prec, float* x, const float* g0, const float
 // hm: 0 = qkv is [rows][3 D] row-major; > 0 = head-major as GemmArgs::hm writes it ([3 heads][hm rows][64], 16-bit
 // modes only; `qkv` is then the base of the whole array and the launch covers sequences from row 0)
 // split: qkv [rows][6 D] and out [rows][2 D] are split images (fp16, not causal; attention.hip attn_tr_kernel<X2>)
-hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads,
+// head_dim: 64 (every route above) or 80 (attn_hd80_kernel: bidirectional, hm == 0, any L <= 1025); else hipErrorInvalidValue
+hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads, int head_dim,
                             bool causal, int qrows, hipStream_t s, bool reverse = false, int hm = 0, bool split = false,
                             unsigned int* fault = nullptr);   // fault: the handle's host-mapped kernel-fault word (attn_ps_kernel)
 

@@ -202,23 +202,35 @@ __global__ __launch_bounds__(256) void count_inexact_kernel(const float* __restr
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, (unsigned long long)mine);
 }
 
-// one workgroup (16 waves) per pooled row; D <= 1024, P <= 1024.  The projection is a chain
+// one workgroup (16 waves) per pooled row; D <= 1024 (WIDE: D <= 1280), P <= 1024.  The projection is a chain
 // of dependent load -> fma -> cross-lane reductions per output feature, so it is spread over
 // 16 waves (32 features each at P=512) rather than 4.
+// WIDE = false is the kernel as it always was, source line for source line (every D <= 1024 launch: the same instruction
+// stream, the same bits); WIDE = true (ViT-H/14's vision tower, 1024 < D <= 1280) gives a thread a second element, tid + 1024.
 constexpr int NWP = 16;
+constexpr int POOL_MAXD = 1280;
+template <bool WIDE>
 __global__ __launch_bounds__(NWP * 64) void pool_project_kernel(
     const float* __restrict__ x, const int32_t* __restrict__ row_idx, int row_stride, int D,
     const float* __restrict__ g, const float* __restrict__ b, float eps,
     const float* __restrict__ proj, int P, float* __restrict__ out, int normalize) {
-  __shared__ float y[1024];
+  __shared__ float y[WIDE ? POOL_MAXD : 1024];
   __shared__ float o[1024];
   __shared__ float red[2 * NWP];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t row = row_idx ? (size_t)row_idx[n] : (size_t)n * row_stride;
   const float* xr = x + row * D;
-  // LayerNorm (two-pass, fp32); D <= 1024 = one element per thread
+  // LayerNorm (two-pass, fp32); D <= 1024 = one element per thread (WIDE: a second one, t2 = tid + 1024 < D)
+  const int t2 = tid + NWP * 64;
   const float xv = tid < D ? xr[tid] : 0.f;
-  float s = wave_sum(xv);
+  float xw = 0.f;
+  float s;
+  if constexpr (WIDE) {
+    if (t2 < D) xw = xr[t2];
+    s = wave_sum(xv + xw);
+  } else {
+    s = wave_sum(xv);
+  }
   if (lane == 0) red[wave] = s;
   __syncthreads();
   float tot = 0.f;
@@ -226,7 +238,14 @@ __global__ __launch_bounds__(NWP * 64) void pool_project_kernel(
   for (int i = 0; i < NWP; ++i) tot += red[i];
   const float mean = tot / (float)D;
   const float c = tid < D ? xv - mean : 0.f;
-  float q = wave_sum(c * c);
+  float cw = 0.f;
+  float q;
+  if constexpr (WIDE) {
+    if (t2 < D) cw = xw - mean;
+    q = wave_sum(fmaf(cw, cw, c * c));
+  } else {
+    q = wave_sum(c * c);
+  }
   if (lane == 0) red[NWP + wave] = q;
   __syncthreads();
   tot = 0.f;
@@ -234,6 +253,9 @@ __global__ __launch_bounds__(NWP * 64) void pool_project_kernel(
   for (int i = 0; i < NWP; ++i) tot += red[NWP + i];
   const float rstd = 1.0f / sqrtf(tot / (float)D + eps);
   if (tid < D) y[tid] = c * rstd * g[tid] + b[tid];
+  if constexpr (WIDE) {
+    if (t2 < D) y[t2] = cw * rstd * g[t2] + b[t2];
+  }
   __syncthreads();
   // projection: wave per output feature, lanes split D
   float sq = 0.f;  // lane 0 of each wave accumulates squares of its outputs
@@ -356,8 +378,15 @@ hipError_t launch_count_inexact(int prec, const float* src, size_t n, unsigned l
 hipError_t launch_pool_project(const float* x, const int32_t* row_idx, int row_stride, int n,
                                int D, const float* g, const float* b, float eps,
                                const float* proj, int P, float* out, hipStream_t s, bool normalize) {
-  if (n <= 0 || D > 1024 || D % 4 || P > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pool_project_kernel, dim3(n), dim3(NWP * 64), 0, s, x, row_idx, row_stride, D, g, b,
-                     eps, proj, P, out, normalize ? 1 : 0);
+  if (n <= 0 || D > POOL_MAXD || D % 4 || P > 1024) return hipErrorInvalidValue;
+  // past 1024 columns only the widths a tower can have (mcm_create: multiples of 64) — the two-elements-per-thread round is
+  // there for ViT-H/14's 1280, not for ragged rows, and what was refused at D <= 1024 + 4 stays refused
+  if (D > 1024 && D % 64) return hipErrorInvalidValue;
+  if (D > 1024)
+    hipLaunchKernelGGL(pool_project_kernel<true>, dim3(n), dim3(NWP * 64), 0, s, x, row_idx, row_stride, D, g, b,
+                       eps, proj, P, out, normalize ? 1 : 0);
+  else
+    hipLaunchKernelGGL(pool_project_kernel<false>, dim3(n), dim3(NWP * 64), 0, s, x, row_idx, row_stride, D, g, b,
+                       eps, proj, P, out, normalize ? 1 : 0);
   return hipGetLastError();
 }

@@ -10,9 +10,9 @@
 
 namespace {
 
-constexpr int MAXV = LN_MAXV;  // float4 per lane: D <= 64*4*4 = 1024
+// MAXV float4 per lane: LN_MAXV = 4 for D <= 1024 (every launch it has always been), LN_WIDEV = 5 for 1024 < D <= 1280
 
-template <int OUT, bool X2 = false>  // OUT = MCM_PREC_F32: fp32 rows; BF16 / F16: packed 16-bit rows (X2: split rows, ys counts their elements)
+template <int OUT, bool X2 = false, int MAXV = LN_MAXV>  // OUT = MCM_PREC_F32: fp32 rows; BF16 / F16: packed 16-bit rows (X2: split rows, ys counts their elements)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x,
                                                         const float* __restrict__ g,
                                                         const float* __restrict__ b, void* y,
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x,
 // the first LayerNorm is written back in place (it is the residual stream) AND, still in registers, normalised again
 // into the first QKV GEMM's operand.  Same arithmetic as the two launches (the second LayerNorm sees exactly the fp32
 // values the first one stores), one 310-MB read of x less.
-template <int OUT, bool X2 = false>
+template <int OUT, bool X2 = false, int MAXV = LN_MAXV>
 __global__ __launch_bounds__(256) void layernorm_pre_kernel(float* x, const float* __restrict__ g0,
                                                             const float* __restrict__ b0,
                                                             const float* __restrict__ g1,
@@ -166,47 +166,54 @@ __global__ __launch_bounds__(256) void fold_stats_kernel(const float2* __restric
 hipError_t launch_layernorm_pre(int prec, float* x, const float* g0, const float* b0, const float* g1,
                                 const float* b1, void* y, int M, int D, float eps, hipStream_t s,
                                 bool reverse, unsigned int* sat, const float* cls, const float* pos0, int ntok, bool split) {
-  if (M <= 0 || D <= 0 || D % 4 || D > 64 * 4 * MAXV) return hipErrorInvalidValue;
+  if (M <= 0 || D <= 0 || D % 4 || D > 64 * 4 * LN_WIDEV) return hipErrorInvalidValue;
   const dim3 grid((M + 3) / 4), block(256);
   const int rev = reverse ? 1 : 0;
+  const bool wide = D > 64 * 4 * LN_MAXV;   // one more float4 per lane
+#define MCM_LN_PRE(OUT, X2)                                                                                                  \
+  do {                                                                                                                       \
+    if (wide) hipLaunchKernelGGL((layernorm_pre_kernel<OUT, X2, LN_WIDEV>), grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1); \
+    else hipLaunchKernelGGL((layernorm_pre_kernel<OUT, X2>), grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1); \
+  } while (0)
   if (split) {  // split rows: fp16 only, whole 64-column blocks
     if (prec != MCM_PREC_F16 || D % 64) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((layernorm_pre_kernel<MCM_PREC_F16, true>), grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1);
+    MCM_LN_PRE(MCM_PREC_F16, true);
     return hipGetLastError();
   }
-  if (prec == MCM_PREC_BF16)
-    hipLaunchKernelGGL(layernorm_pre_kernel<MCM_PREC_BF16>, grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1);
-  else if (prec == MCM_PREC_F16)
-    hipLaunchKernelGGL(layernorm_pre_kernel<MCM_PREC_F16>, grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1);
-  else
-    hipLaunchKernelGGL(layernorm_pre_kernel<MCM_PREC_F32>, grid, block, 0, s, x, g0, b0, g1, b1, y, M, D, eps, rev, sat, cls, pos0, ntok > 0 ? ntok : 1);
+  if (prec == MCM_PREC_BF16) MCM_LN_PRE(MCM_PREC_BF16, false);
+  else if (prec == MCM_PREC_F16) MCM_LN_PRE(MCM_PREC_F16, false);
+  else MCM_LN_PRE(MCM_PREC_F32, false);
+#undef MCM_LN_PRE
   return hipGetLastError();
 }
 
 hipError_t launch_layernorm(int prec, const float* x, const float* g, const float* b, void* y,
                             int M, int D, float eps, bool out_f32, hipStream_t s, size_t x_stride,
                             size_t y_stride, bool reverse, unsigned int* sat, bool split) {
-  if (M <= 0 || D <= 0 || D % 4 || D > 64 * 4 * MAXV) return hipErrorInvalidValue;
+  if (M <= 0 || D <= 0 || D % 4 || D > 64 * 4 * LN_WIDEV) return hipErrorInvalidValue;
   const size_t xs = x_stride ? x_stride : (size_t)D, ys = y_stride ? y_stride : (size_t)D * (split ? 2 : 1);
   if (xs % 4 || ys % 4) return hipErrorInvalidValue;
-  if (split) {  // split rows (y_stride counts the split row's elements): fp16 only, whole 64-column blocks
-    if (prec != MCM_PREC_F16 || out_f32 || D % 64) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((layernorm_kernel<MCM_PREC_F16, true>), dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, y, M, D, eps, xs, ys,
-                       reverse ? 1 : 0, 1, sat);
-    return hipGetLastError();
-  }
   const dim3 grid((M + 3) / 4), block(256);
   const int rev = reverse ? 1 : 0;
+  const bool wide = D > 64 * 4 * LN_MAXV;   // one more float4 per lane
   // x is streamed with the non-temporal hint: the 310-MB residual read would otherwise push the
   // 155 MB of LayerNorm output — the next GEMM's X operand — out of L2 / Infinity Cache
   // (measured: GEMM time -4 %, +3.3 % end to end).
   constexpr int nt = 1;
-  if (prec == MCM_PREC_BF16 && !out_f32)
-    hipLaunchKernelGGL(layernorm_kernel<MCM_PREC_BF16>, grid, block, 0, s, x, g, b, y, M, D, eps, xs, ys, rev, nt, sat);
-  else if (prec == MCM_PREC_F16 && !out_f32)
-    hipLaunchKernelGGL(layernorm_kernel<MCM_PREC_F16>, grid, block, 0, s, x, g, b, y, M, D, eps, xs, ys, rev, nt, sat);
-  else
-    hipLaunchKernelGGL(layernorm_kernel<MCM_PREC_F32>, grid, block, 0, s, x, g, b, y, M, D, eps, xs, ys, rev, nt, sat);
+#define MCM_LN(OUT, X2)                                                                                                  \
+  do {                                                                                                                   \
+    if (wide) hipLaunchKernelGGL((layernorm_kernel<OUT, X2, LN_WIDEV>), grid, block, 0, s, x, g, b, y, M, D, eps, xs, ys, rev, nt, sat); \
+    else hipLaunchKernelGGL((layernorm_kernel<OUT, X2>), grid, block, 0, s, x, g, b, y, M, D, eps, xs, ys, rev, nt, sat); \
+  } while (0)
+  if (split) {  // split rows (y_stride counts the split row's elements): fp16 only, whole 64-column blocks
+    if (prec != MCM_PREC_F16 || out_f32 || D % 64) return hipErrorInvalidValue;
+    MCM_LN(MCM_PREC_F16, true);
+    return hipGetLastError();
+  }
+  if (prec == MCM_PREC_BF16 && !out_f32) MCM_LN(MCM_PREC_BF16, false);
+  else if (prec == MCM_PREC_F16 && !out_f32) MCM_LN(MCM_PREC_F16, false);
+  else MCM_LN(MCM_PREC_F32, false);
+#undef MCM_LN
   return hipGetLastError();
 }
 

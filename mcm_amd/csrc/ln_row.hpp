@@ -12,6 +12,9 @@
 #include "common.hpp"
 
 constexpr int LN_MAXV = 4;  // float4 per lane: D <= 64 * 4 * 4 = 1024
+constexpr int LN_WIDEV = 5; // the wide instantiations of layernorm.hip: D <= 1280 (ViT-H/14's vision tower)
+// Every function takes the row as float4 (&v)[NV] with NV deduced from the caller's array: NV = LN_MAXV is the code it has
+// always been (the GEMM tail and every D <= 1024 launch), NV = LN_WIDEV one more vector per lane in the same order.
 
 // A lane holds v[i] = columns (i * 64 + lane) * 4 .. + 3 of the row.  NVU > 0: the caller guarantees D == NVU * 256, so
 // "column < D" is the compile-time test i < NVU (no per-lane branches); NVU == 0: any D that is a multiple of 4.
@@ -20,12 +23,12 @@ __device__ __forceinline__ bool ln_has(int i, int lane, int D) {
   if constexpr (NVU > 0) return i < NVU;
   else return (i * 64 + lane) * 4 < D;
 }
-template <int NVU = 0>
-__device__ __forceinline__ float ln_part_sum(const float4 (&v)[LN_MAXV], int D, int lane) {
+template <int NVU = 0, int NV>
+__device__ __forceinline__ float ln_part_sum(const float4 (&v)[NV], int D, int lane) {
 #pragma clang fp contract(off)
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i)
+  for (int i = 0; i < NV; ++i)
     if (ln_has<NVU>(i, lane, D)) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   return s;
 }
@@ -34,12 +37,12 @@ __device__ __forceinline__ float ln_mean(float wave_total, int D) {
   return wave_total / (float)D;
 }
 // centres the row in place and returns this lane's part of the sum of squares
-template <int NVU = 0>
-__device__ __forceinline__ float ln_center_sq(float4 (&v)[LN_MAXV], float mean, int D, int lane) {
+template <int NVU = 0, int NV>
+__device__ __forceinline__ float ln_center_sq(float4 (&v)[NV], float mean, int D, int lane) {
 #pragma clang fp contract(off)
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i)
+  for (int i = 0; i < NV; ++i)
     if (ln_has<NVU>(i, lane, D)) {
       v[i].x -= mean; v[i].y -= mean; v[i].z -= mean; v[i].w -= mean;
       q += __builtin_fmaf(v[i].x, v[i].x, v[i].y * v[i].y) + __builtin_fmaf(v[i].z, v[i].z, v[i].w * v[i].w);
@@ -50,12 +53,12 @@ __device__ __forceinline__ float ln_rstd(float wave_total_sq, int D, float eps) 
 #pragma clang fp contract(off)
   return 1.0f / sqrtf(wave_total_sq / (float)D + eps);
 }
-template <int NVU = 0>
-__device__ __forceinline__ void ln_scale(float4 (&v)[LN_MAXV], float rstd, const float* __restrict__ g,
+template <int NVU = 0, int NV>
+__device__ __forceinline__ void ln_scale(float4 (&v)[NV], float rstd, const float* __restrict__ g,
                                          const float* __restrict__ b, int D, int lane) {
 #pragma clang fp contract(off)
 #pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int d = (i * 64 + lane) * 4;
     if (ln_has<NVU>(i, lane, D)) {
       const float4 gv = *(const float4*)(g + d);
@@ -68,8 +71,8 @@ __device__ __forceinline__ void ln_scale(float4 (&v)[LN_MAXV], float rstd, const
   }
 }
 // on return v holds LayerNorm(row) * g + b in fp32
-template <int NVU = 0>
-__device__ __forceinline__ void ln_row_apply(float4 (&v)[LN_MAXV], const float* __restrict__ g, const float* __restrict__ b,
+template <int NVU = 0, int NV>
+__device__ __forceinline__ void ln_row_apply(float4 (&v)[NV], const float* __restrict__ g, const float* __restrict__ b,
                                              int D, float eps, int lane) {
   const float mean = ln_mean(wave_sum(ln_part_sum<NVU>(v, D, lane)), D);
   const float rstd = ln_rstd(wave_sum(ln_center_sq<NVU>(v, mean, D, lane)), D, eps);
@@ -78,10 +81,10 @@ __device__ __forceinline__ void ln_row_apply(float4 (&v)[LN_MAXV], const float* 
 
 // the row in the operand dtype OUT (fp32: as it is) to yrow; X2 (16-bit OUT): as a split image of 2 D elements, per 64
 // columns hi[64] then lo[64] (GemmArgs::xsplit)
-template <int OUT, int NVU = 0, bool X2 = false>
-__device__ __forceinline__ void ln_row_store(const float4 (&v)[LN_MAXV], void* yrow, int D, int lane, float& amax) {
+template <int OUT, int NVU = 0, bool X2 = false, int NV>
+__device__ __forceinline__ void ln_row_store(const float4 (&v)[NV], void* yrow, int D, int lane, float& amax) {
 #pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int d = (i * 64 + lane) * 4;
     if (ln_has<NVU>(i, lane, D)) {
       if constexpr (OUT != MCM_PREC_F32 && X2) {

@@ -218,7 +218,8 @@ int g_nsplit = 1;  // A/B (mcm_debug_nsplit): the wide store GEMMs (QKV, fc1) as
 hipError_t gemm(mcm_handle* h, hipStream_t s, int prec, int epi, const GemmArgs& a_in) {
   GemmArgs a = a_in;
 #ifdef MCM_HARNESS
-  if (g_nsplit > 1 && (epi == EPI_STORE || epi == EPI_GELU) && a.N >= 2048 && a.N % (256 * g_nsplit) == 0 && !a.fold_rs && !a.hm && a.M > 4096) {
+  // (N = 3 x 768 / 3 x 1024 / 3072 / 4096 only: like the other arms it does not learn ViT-H/14's 3840 / 5120 columns)
+  if (g_nsplit > 1 && (epi == EPI_STORE || epi == EPI_GELU) && a.K <= 1024 && a.N <= 4096 && a.N >= 2048 && a.N % (256 * g_nsplit) == 0 && !a.fold_rs && !a.hm && a.M > 4096) {
     // W re-fetch experiment: the XCD's L2 (4 MiB) cannot hold all of W (fc1: 4.7 MB) beside the X
     // panels in flight, so W streams through it once per tile round; with the columns cut in n blocks only N / n of W
     // is live per launch (X is then read n times).  Same bits (a column's K-sum does not depend on its neighbours).
@@ -282,14 +283,15 @@ hipError_t lnorm(mcm_handle* h, hipStream_t s, int prec, const float* x, const f
                           h->sat_on ? h->sat_dev : nullptr);
 }
 // seq0: first sequence of the launch (a chunk of the batch starts there)
-hipError_t attn(mcm_handle* h, hipStream_t s, int prec, int nseq, int L, int heads, bool causal,
+// hd: head_dim (64, or 80 in ViT-H/14's vision tower)
+hipError_t attn(mcm_handle* h, hipStream_t s, int prec, int nseq, int L, int heads, int hd, bool causal,
                 int qrows = 0, int seq0 = 0, int hm = 0, bool split = false) {
   const int q = qrows > 0 ? qrows : L;
-  Scope sc(h, s, MCM_KC_ATTENTION, 4.0 * nseq * heads * (double)q * L * 64 * (causal ? 0.5 : 1.0));
-  if (split) return launch_attention(prec, h->qkv, h->att, nseq, L, heads, causal, qrows, s, next_dir(h), 0, true);
-  const size_t es = prec_esize(prec), D = (size_t)heads * 64, row0 = (size_t)seq0 * L;
+  Scope sc(h, s, MCM_KC_ATTENTION, 4.0 * nseq * heads * (double)q * L * hd * (causal ? 0.5 : 1.0));
+  if (split) return launch_attention(prec, h->qkv, h->att, nseq, L, heads, hd, causal, qrows, s, next_dir(h), 0, true);
+  const size_t es = prec_esize(prec), D = (size_t)heads * hd, row0 = (size_t)seq0 * L;
   return launch_attention(prec, (const char*)h->qkv + row0 * 3 * D * es, (char*)h->att + row0 * D * es, nseq, L,
-                          heads, causal, qrows, s, next_dir(h), hm, false, h->fault_dev);
+                          heads, hd, causal, qrows, s, next_dir(h), hm, false, h->fault_dev);
 }
 // A/B arm (harness: mcm_debug_qkv_head_major): qkv of the 16-bit towers head-major ([3 heads][rows][64],
 // GemmArgs::hm) between the QKV projection and attention.  Bit-identical; attention 1.63 -> 1.56 ms per step, the QKV
@@ -395,10 +397,13 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
   const int Mp = (int)padded_rows(h, M);
   const int ks = t.split ? 1 : 0;
   const int xs = x2 ? 1 : 0;
+  const int hd = D / t.heads;  // 64, or 80 (mcm_create admits nothing else)
+  // the harness A/B arms (LayerNorm fold / tail / cluster / ROW64, head-major qkv) know head_dim 64 and widths <= 1024 only
+  const bool arms_ok = hd == 64 && D <= 1024;
   const bool erf = t.act == MCM_ACT_GELU;  // the tower's MLP activation: exact GELU (OpenCLIP-trained) or QuickGELU (OpenAI)
   const int epi_store = x2 ? EPI_STORE_X2 : EPI_STORE;
   const int epi_act = erf ? (x2 ? EPI_GELU_ERF_X2 : EPI_GELU_ERF) : (x2 ? EPI_GELU_X2 : EPI_GELU);
-  if (x2 || erf) fold_ok = false;  // (the LayerNorm fold's consumer epilogue is an A/B arm: QuickGELU only)
+  if (x2 || erf || !arms_ok) fold_ok = false;  // (the LayerNorm fold's consumer epilogue is an A/B arm: QuickGELU only)
   const size_t wrow = (size_t)D * es * (t.split ? 2 : 1);  // bytes per row of a [*, D] weight image
   // producer form: 1 = fused into the residual GEMM's epilogue (ping-pong kernel), 2 = plain residual GEMM + fold_rows
   // (tile kernel: small batches) - bit-identical; the consumers need a fold epilogue in whichever kernel they take
@@ -417,11 +422,11 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
   };
   bool ln1_folded = false;  // h->ln holds gamma1 o x and h->fold_rs the row statistics of this layer's layer_norm1
   // LayerNorm in the tail: the residual GEMMs of whole-batch layers also produce the LayerNorm that follows them
-  const bool tail_ok0 = g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && Mp % 256 == 0 && Mp / 256 <= h->ln_cap8 * 8 &&
+  const bool tail_ok0 = arms_ok && g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && Mp % 256 == 0 && Mp / 256 <= h->ln_cap8 * 8 &&
                         gemm_ln_tail_ok(P, Mp, D);
   // LayerNorm by the row panel's cluster (LNC, harness arm): the same hand-over of gamma / beta / output / counters, plus the
   // slot-moment buffer; the residual epilogue itself writes the LayerNorm output (no idle-wave tickets, no re-read of x)
-  const bool cluster_ok = g_ln_cluster && !g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && h->fold_part && Mp % 256 == 0 &&
+  const bool cluster_ok = arms_ok && g_ln_cluster && !g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && h->fold_part && Mp % 256 == 0 &&
                           2 * ((Mp / 256 + 7) / 8) <= h->ln_cap8 && gemm_ln_tail_ok(P, Mp, D);
   auto with_tail = [&](GemmArgs& g, const float* gamma, const float* beta) {
     g.ln_g = gamma; g.ln_b = beta; g.ln_y = h->ln; g.ln_eps = h->cfg.ln_eps;
@@ -441,7 +446,7 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
 #endif
   };
   // ROW64 arm (harness): the residual GEMM as 64-row full-row tiles whose epilogue writes x and the LayerNorm output
-  const bool row_ok = g_ln_row && !g_ln_tail && !g_ln_cluster && !x2 && !can_fold && !t.split && P != MCM_PREC_F32 && Mp % 64 == 0 &&
+  const bool row_ok = arms_ok && g_ln_row && !g_ln_tail && !g_ln_cluster && !x2 && !can_fold && !t.split && P != MCM_PREC_F32 && Mp % 64 == 0 &&
                       (D == 768 || D == 1024) && t.ff % 128 == 0;
   auto row_gemm = [&](GemmArgs g, const float* gamma, const float* beta, void** blk) -> hipError_t {
 #ifdef MCM_HARNESS
@@ -485,7 +490,7 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
         const int hm = (g_qkv_head_major && !x2 && nch == 1 && P != MCM_PREC_F32 && t.heads * 64 == D) ? Mp : 0;
         a.hm = hm;
         HIP_TRY(h, gemm(h, s, P, epi_store, a));
-        HIP_TRY(h, attn(h, s, P, sq, L, t.heads, causal, 0, c * sq, hm, x2));
+        HIP_TRY(h, attn(h, s, P, sq, L, t.heads, hd, causal, 0, c * sq, hm, x2));
       }
     } else {
       GemmArgs kv{};  // K and V of every token: weight rows [D, 3D), output columns [D, 3D)
@@ -497,7 +502,7 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
       q.x = h->ln; q.w = w.wqkv; q.bias = w.bqkv; q.out = h->qkv;
       q.M = nseq; q.N = D; q.K = D; q.ldx = L * D; q.ldo = L * 3 * D; q.ksplit = ks; q.xsplit = xs;
       HIP_TRY(h, gemm(h, s, P, epi_store, q));
-      HIP_TRY(h, attn(h, s, P, nseq, L, t.heads, causal, 1, 0, 0, x2));
+      HIP_TRY(h, attn(h, s, P, nseq, L, t.heads, hd, causal, 1, 0, 0, x2));
     }
     const int Mr = cls ? nseq : M;            // rows that continue
     const int rs = cls ? L * D : D;           // their stride in x / att
@@ -622,13 +627,14 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
   if ((c.v_hidden_act != MCM_ACT_QUICK_GELU && c.v_hidden_act != MCM_ACT_GELU) ||
       (c.t_hidden_act != MCM_ACT_QUICK_GELU && c.t_hidden_act != MCM_ACT_GELU))
     return fail(nullptr, MCM_EINVAL, "unknown hidden_act (MCM_ACT_QUICK_GELU or MCM_ACT_GELU)");
-  if (c.v_heads <= 0 || c.t_heads <= 0 || c.v_width != c.v_heads * 64 || c.t_width != c.t_heads * 64)
-    return fail(nullptr, MCM_EINVAL, "head_dim must be 64");
+  if (c.v_heads <= 0 || c.t_heads <= 0 || (c.v_width != c.v_heads * 64 && c.v_width != c.v_heads * 80) ||
+      c.t_width != c.t_heads * 64)
+    return fail(nullptr, MCM_EINVAL, "head_dim must be 64 or 80 in the vision tower (attn_hd80_kernel) and 64 in the text tower");
   if (c.patch_size <= 0 || c.image_size % c.patch_size)
     return fail(nullptr, MCM_EINVAL, "image_size must be a multiple of patch_size");
-  if (c.v_width % 64 || c.t_width % 64 || c.v_mlp % 64 || c.t_mlp % 64 || c.v_width > 1024 ||
+  if (c.v_width % 64 || c.t_width % 64 || c.v_mlp % 64 || c.t_mlp % 64 || c.v_width > 1280 ||
       c.t_width > 1024 || c.proj_dim % 4 || c.proj_dim > 1024)
-    return fail(nullptr, MCM_EINVAL, "widths must be multiples of 64 and <= 1024; proj_dim % 4 == 0");
+    return fail(nullptr, MCM_EINVAL, "widths must be multiples of 64, v_width <= 1280, t_width <= 1024; proj_dim % 4 == 0, <= 1024");
   if (c.max_batch <= 0 || c.max_prompt_tokens <= 0 || c.max_positions <= 0 ||
       c.max_prompt_tokens < c.max_positions)
     return fail(nullptr, MCM_EINVAL, "bad workspace bounds");
@@ -722,7 +728,8 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
     rc = fail(h, MCM_ENOMEM, "hipHostMalloc rowidx");
   if (!rc) rc = dev_alloc(h, (void**)&h->prep_dev, (size_t)mcm_handle::PREP_RING * c.max_batch * sizeof(PrepImage));
 #if defined(MCM_HARNESS) || defined(MCM_LN_FOLD)  // LayerNorm fold (A/B arm): row moments and row statistics
-  if (!rc && c.precision != MCM_PREC_F32 && c.v_width % 256 == 0 && c.v_mlp % 256 == 0) {
+  if (!rc && c.precision != MCM_PREC_F32 && c.v_width % 256 == 0 && c.v_mlp % 256 == 0 && c.v_width <= 1024 &&
+      c.v_width == c.v_heads * 64) {   // (the arm knows head_dim 64 and widths <= 1024: run_layers arms_ok)
     rc = dev_alloc(h, (void**)&h->fold_part, (size_t)(c.v_width / 64) * mv * sizeof(float2));
     if (!rc) rc = dev_alloc(h, (void**)&h->fold_rs, (size_t)mv * sizeof(float2));
   }
@@ -1410,14 +1417,14 @@ int mcm_op_layernorm_split(mcm_handle* h, const float* x_dev, const float* gamma
 int mcm_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                            int32_t heads, void* stream) {
   if (!h) return MCM_EINVAL;
-  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, false, 0, (hipStream_t)stream, false, 0, true));
+  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, 64, false, 0, (hipStream_t)stream, false, 0, true));
   return MCM_OK;
 }
 
 int mcm_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev, int32_t nseq,
                      int32_t seq_len, int32_t heads, int32_t causal, void* stream) {
   if (!h) return MCM_EINVAL;
-  HIP_TRY(h, launch_attention(prec, qkv_dev, out_dev, nseq, seq_len, heads, causal != 0, 0,
+  HIP_TRY(h, launch_attention(prec, qkv_dev, out_dev, nseq, seq_len, heads, 64, causal != 0, 0,
                               (hipStream_t)stream, false, 0, false, h->fault_dev));
   return MCM_OK;
 }
@@ -1467,8 +1474,19 @@ int mcm_debug_clear_faults(mcm_handle* h) {
 int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                            int32_t heads, int32_t causal, int32_t qrows, int32_t reverse, void* stream) {
   if (!h) return MCM_EINVAL;
-  HIP_TRY(h, launch_attention(prec, qkv_dev, out_dev, nseq, seq_len, heads, causal != 0, qrows, (hipStream_t)stream, reverse != 0, 0, false,
+  HIP_TRY(h, launch_attention(prec, qkv_dev, out_dev, nseq, seq_len, heads, 64, causal != 0, qrows, (hipStream_t)stream, reverse != 0, 0, false,
                               h->fault_dev));
+  return MCM_OK;
+}
+
+// the same with the head width as an argument: 64 takes mcm_debug_op_attention's routes, 80 the streaming family of ViT-H/14's
+// vision tower (attn_hd80_kernel: bidirectional only, seq_len <= 1025); qkv [nseq seq_len, 3 heads head_dim], head h at column
+// h head_dim of q, k and v.  A refused argument launches nothing.
+int mcm_debug_op_attention_hd(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                              int32_t heads, int32_t head_dim, int32_t causal, int32_t qrows, int32_t reverse, void* stream) {
+  if (!h) return MCM_EINVAL;
+  HIP_TRY(h, launch_attention(prec, qkv_dev, out_dev, nseq, seq_len, heads, head_dim, causal != 0, qrows, (hipStream_t)stream,
+                              reverse != 0, 0, false, h->fault_dev));
   return MCM_OK;
 }
 
@@ -1477,7 +1495,17 @@ int mcm_debug_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, voi
 int mcm_debug_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
                                  int32_t heads, int32_t qrows, int32_t reverse, void* stream) {
   if (!h) return MCM_EINVAL;
-  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, false, qrows, (hipStream_t)stream,
+  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, 64, false, qrows, (hipStream_t)stream,
+                              reverse != 0, 0, true));
+  return MCM_OK;
+}
+
+// ... and with the head width: split images "per 64 columns hi[64] then lo[64]" over the whole heads x head_dim row, so at
+// head_dim 80 a head straddles blocks (column c of a row at (c / 64) 128 + c % 64, lo 64 further)
+int mcm_debug_op_attention_split_hd(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
+                                    int32_t heads, int32_t head_dim, int32_t qrows, int32_t reverse, void* stream) {
+  if (!h) return MCM_EINVAL;
+  HIP_TRY(h, launch_attention(MCM_PREC_F16, qkv_dev, out_dev, nseq, seq_len, heads, head_dim, false, qrows, (hipStream_t)stream,
                               reverse != 0, 0, true));
   return MCM_OK;
 }
@@ -1535,7 +1563,7 @@ int mcm_debug_op_pool_project(mcm_handle* h, const float* x_dev, int64_t x_rows,
   const bool refused = e == hipErrorInvalidValue;  // the launcher's own shape guard: nothing was launched
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (idx_dev) (void)hipFree(idx_dev);
-  if (refused) return fail(h, MCM_EINVAL, "launch_pool_project refused the shape (D <= 1024, D % 4 == 0, P <= 1024)");
+  if (refused) return fail(h, MCM_EINVAL, "launch_pool_project refused the shape (D <= 1280, D % 4 == 0 — D % 64 == 0 past 1024 —, P <= 1024)");
   HIP_TRY(h, e);
   return MCM_OK;
 }

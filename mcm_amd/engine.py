@@ -113,6 +113,8 @@ def load_library(harness: bool = False):
         L.mcm_debug_persistent_grid.argtypes = [i32]
         L.mcm_debug_op_attention.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
         L.mcm_debug_op_attention_split.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        L.mcm_debug_op_attention_hd.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+        L.mcm_debug_op_attention_split_hd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
         L.mcm_debug_vision_front.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.mcm_debug_op_pool_project.argtypes = [vp, vp, ctypes.c_int64, vp, i32, i32, i32, vp, vp, f32, vp, i32, vp, i32, vp]
         L.mcm_debug_op_text_embed.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]
@@ -172,7 +174,7 @@ HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant",
                         "mcm_debug_clear_faults", "mcm_debug_ln_cluster", "mcm_debug_ln_cluster_spin",
                         "mcm_debug_ln_cluster_deferred", "mcm_debug_ln_row", "mcm_debug_op_attention_split",
                         "mcm_debug_vision_front", "mcm_debug_op_pool_project", "mcm_debug_op_text_embed",
-                        "mcm_debug_op_act"]
+                        "mcm_debug_op_act", "mcm_debug_op_attention_hd", "mcm_debug_op_attention_split_hd"]
 
 
 def _stream_ptr():

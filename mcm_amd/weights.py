@@ -177,7 +177,9 @@ def check_hidden_act(path: str, geo: ClipGeometry) -> None:
     geometry's; ValueError names both and the `--CLIP_ckpt` that matches.  Without a `config.json` nothing can be checked:
     one log line says which activation is assumed — a warning when a geometry of the same shape with the other activation
     exists (the mix-up is possible), else at info level."""
-    from .config import CHECKPOINTS, TEST_GEOMETRIES
+    from .config import TEST_GEOMETRIES, all_checkpoints
+
+    CHECKPOINTS = all_checkpoints()
 
     log = logging.getLogger("mcm_amd")
     cfg_path = checkpoint_config_path(path)
