@@ -282,6 +282,10 @@ int mcm_reduce_bank(mcm_handle* h, const float* feats_dev, int32_t K, int32_t T,
  * (get_and_print_results, :255: the stored scores are negated confidences).
  * out_host[0..2] = AUROC, AUPR, FPR at the operating point whose recall is closest to
  * recall_level (0.95 in the reference), same tie rules as the reference.  Synchronises `stream`.
+ * NON-FINITE SCORES: -inf and +inf are ordinary ordered scores (below / above every finite one, equal to
+ * themselves); -0.0 ties +0.0; subnormal scores are distinct numbers.  A NaN has no place in the order: one
+ * NaN anywhere in either vector makes all three outputs NaN (the call still returns MCM_OK), never a
+ * finite number.  (The host route, sklearn, raises on any non-finite score instead.)
  * Scratch (12 bytes per score) is borrowed from the activation workspace mcm_create sized (the B/16
  * batch-512 workspace holds 25 million scores); larger inputs get a one-off stream-ordered allocation
  * (hipMallocAsync / hipFreeAsync on `stream`).
@@ -294,7 +298,10 @@ int mcm_measures(mcm_handle* h, const float* pos_dev, int64_t n_pos, const float
 /* Fixed-edge histogram of a device score vector: the constant-size per-rank payload `north_star` names
  * ("RCCL all-gather of per-shard score histograms"), summed over ranks by the caller's all-reduce.
  * edges_dev: fp32 [n_bins + 1] ascending; counts_dev: int64 [n_bins], overwritten.  numpy.histogram
- * semantics (bin i = [e_i, e_{i+1}), last bin closed, out-of-range scores dropped); n_bins <= 8192. */
+ * semantics (bin i = [e_i, e_{i+1}), last bin closed, out-of-range scores dropped); n_bins <= 8192.
+ * As numpy does with explicit bins, -inf, +inf and NaN scores are counted nowhere; repeated edges make
+ * zero-width bins that stay empty (a score equal to a repeated LAST edge lands in the last bin).  n == 0 is
+ * allowed (scores_dev may then be NULL): all counts are zero. */
 int mcm_score_histogram(mcm_handle* h, const float* scores_dev, int64_t n, const float* edges_dev,
                         int32_t n_bins, int64_t* counts_dev, void* stream);
 

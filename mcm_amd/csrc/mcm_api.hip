@@ -1231,7 +1231,7 @@ int mcm_measures(mcm_handle* h, const float* pos_dev, int64_t n_pos, const float
 int mcm_score_histogram(mcm_handle* h, const float* scores_dev, int64_t n, const float* edges_dev,
                         int32_t n_bins, int64_t* counts_dev, void* stream) {
   if (!h) return MCM_EINVAL;
-  if (!scores_dev || !edges_dev || !counts_dev || n < 0 || n_bins <= 0)
+  if ((!scores_dev && n) || !edges_dev || !counts_dev || n < 0 || n_bins <= 0)  // n == 0: all-zero counts, no vector needed
     return fail(h, MCM_EINVAL, "bad argument");
   if (n_bins > 8192) return fail(h, MCM_ERANGE, "at most 8192 bins");
   HIP_TRY(h, launch_histogram(scores_dev, (long)n, edges_dev, n_bins, (unsigned long long*)counts_dev,

@@ -16,13 +16,17 @@
 //           recall tp_j/n_pos is closest to the level, ties resolved towards the LOWEST threshold
 //           (the reversed-slice argmin of :100-106 scans from full recall downwards).
 // Comparisons are on the fp32 scores (as the reference's float32 arrays), recall / precision
-// arithmetic is fp64 like numpy's.
+// arithmetic is fp64 like numpy's.  -inf and +inf are ordinary ordered scores; a NaN has no place
+// in the order, so one NaN in either vector turns all three outputs into NaN.
 #include "common.hpp"
 
 namespace {
 
 constexpr int CT = 256;     // threads per counting workgroup = examples per workgroup
 constexpr int TILE = 4096;  // staged comparison values per LDS tile
+// The tail of a ragged tile must count for no score.  NaN compares false against everything, -inf and +inf (ordinary
+// scores) included; a -inf pad would be `>=` a -inf score and over-count it by the pad length.
+constexpr float TILE_PAD = __builtin_nanf("");
 
 __device__ __forceinline__ float ex_at(const float* pos, long n_pos, const float* neg, long i, float sgn) {
   return sgn * (i < n_pos ? pos[i] : neg[i - n_pos]);
@@ -40,7 +44,7 @@ __global__ __launch_bounds__(CT) void count_kernel(const float* __restrict__ pos
   for (long j0 = 0; j0 < n_pos; j0 += TILE) {
     const int m = (int)((n_pos - j0) < TILE ? (n_pos - j0) : TILE);
     __syncthreads();
-    for (int j = threadIdx.x; j < TILE; j += CT) tile[j] = j < m ? sgn * pos[j0 + j] : -INFINITY;
+    for (int j = threadIdx.x; j < TILE; j += CT) tile[j] = j < m ? sgn * pos[j0 + j] : TILE_PAD;
     __syncthreads();
 #pragma unroll 4
     for (int j = 0; j < TILE; j += 4) {  // wave-uniform address: LDS broadcast reads
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(CT) void count_kernel(const float* __restrict__ pos
   for (long j0 = 0; j0 < n_neg; j0 += TILE) {
     const int m = (int)((n_neg - j0) < TILE ? (n_neg - j0) : TILE);
     __syncthreads();
-    for (int j = threadIdx.x; j < TILE; j += CT) tile[j] = j < m ? sgn * neg[j0 + j] : -INFINITY;
+    for (int j = threadIdx.x; j < TILE; j += CT) tile[j] = j < m ? sgn * neg[j0 + j] : TILE_PAD;
     __syncthreads();
 #pragma unroll 4
     for (int j = 0; j < TILE; j += 4) {
@@ -110,8 +114,10 @@ __global__ __launch_bounds__(RT) void measures_kernel(const float* __restrict__ 
   // operating point: min |recall - level|, then lowest threshold
   double bd = INFINITY;
   float bs = INFINITY;
+  int nan_seen = 0;  // this loop reads every score once: a NaN anywhere makes the whole result NaN (include/mcm.h)
   for (long i = tid; i < n; i += RT) {
     const float s = ex_at(pos, n_pos, neg, i, sgn);
+    nan_seen |= s != s;
     if (!(s >= minpos)) continue;
     const double d = fabs((double)tp[i] / (double)n_pos - level);
     if (d < bd || (d == bd && s < bs)) { bd = d; bs = s; }
@@ -124,7 +130,10 @@ __global__ __launch_bounds__(RT) void measures_kernel(const float* __restrict__ 
   for (long i = tid; i < n; i += RT)
     if (ex_at(pos, n_pos, neg, i, sgn) == gs) pick = fp[i];
   pick = block_reduce(pick, red_u, [](unsigned long long a, unsigned long long b) { return a > b ? a : b; });
-  if (tid == 0) {
+  nan_seen = __syncthreads_or(nan_seen);
+  if (tid == 0 && nan_seen) {
+    out[0] = out[1] = out[2] = out[3] = __builtin_nan("");
+  } else if (tid == 0) {
     out[0] = (double)u2 / (2.0 * (double)n_pos * (double)n_neg);
     out[1] = ap / (double)n_pos;
     out[2] = (double)pick / (double)n_neg;
@@ -163,7 +172,7 @@ __global__ __launch_bounds__(256) void hist_kernel(const float* __restrict__ x, 
 
 hipError_t launch_histogram(const float* x, long n, const float* edges, int nb, unsigned long long* counts,
                             hipStream_t s) {
-  if (!x || !edges || !counts || n < 0 || nb <= 0 || nb > HB_MAX) return hipErrorInvalidValue;
+  if ((!x && n) || !edges || !counts || n < 0 || nb <= 0 || nb > HB_MAX) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(counts, 0, (size_t)nb * sizeof(unsigned long long), s);
   if (e != hipSuccess || n == 0) return e;
   const long blocks = (n + 255) / 256;

@@ -245,6 +245,74 @@ def score_budget(img, txt, T: float, kind: int):
     return ref, bud + 0.5 * ulp(ref, "fp32")
 
 
+# ---- Mahalanobis --------------------------------------------------------------------------------------------------------
+U64 = 2.0 ** -53    # unit roundoff of fp64
+# An fp64 dot product of P terms is off by at most P u64 sum |a||b| whatever the order (gamma_P).  Each of the three terms of
+# d = q - W.f + k is two such levels deep: q = sum_p f_p (P f)_p and k = sum_p mu_p (P mu)_p are a sum of P inner dot
+# products, W.f a dot product with a W whose elements are themselves P-term dot products: 2 P u64 of the absolute sums.
+# The score is 0.5 d (an exact product), so in terms of the score the constant is 0.5 * 2.
+C_MAHA = 1.0
+
+
+def maha_reference(feats, means, prec):
+    """fp64 min_c 0.5 (f - mu_c)^T P (f - mu_c), the direct form of reference utils/detection_util.py:176-207 on the fp32
+    inputs (the differences are taken in fp64; P is used as given, not symmetrised).  Returns (score [B], argmin [B])."""
+    f64, m64, p64 = (np.asarray(a, np.float64) for a in (feats, means, prec))
+    score, arg = np.empty(f64.shape[0]), np.empty(f64.shape[0], np.int64)
+    for b in range(f64.shape[0]):
+        d = f64[b][None, :] - m64                                     # [C, P]
+        v = 0.5 * np.einsum("cp,cp->c", d @ p64, d)
+        arg[b] = int(np.argmin(v))
+        score[b] = v[arg[b]]
+    return score, arg
+
+
+def maha_budget(feats, means, prec):
+    """(ref, budget) of maha_prepare_kernel + maha_score_kernel (score.hip): W_c = P mu_c + P^T mu_c and k_c = mu_c^T P mu_c
+    accumulated in fp64 once per class, then per feature q = f^T P f and W_c . f in fp64, d_c = q - W_c . f + k_c (the three
+    terms cancel when f is near mu_c: the error is relative to the terms, not to d), the minimum over the classes, one
+    product with 0.5 (exact) and one rounding to fp32:
+      0.5 ulp32(ref) + C_MAHA P u64 (|f|^T |P| |f| + |W_c| . |f| + |mu_c|^T |P| |mu_c|) at the reference's arg-min class c,
+    the accumulation term with score_budget's 1 % slack."""
+    f64, m64, p64 = (np.asarray(a, np.float64) for a in (feats, means, prec))
+    P = p64.shape[0]
+    ref, arg = maha_reference(feats, means, prec)
+    pa = np.abs(p64)
+    mu = m64[arg]                                                     # [B, P]
+    w = mu @ p64.T + mu @ p64                                         # P mu + P^T mu per row
+    fa, ma = np.abs(f64), np.abs(mu)
+    terms = np.einsum("bp,bp->b", fa @ pa.T, fa) + np.einsum("bp,bp->b", np.abs(w), fa) + np.einsum("bp,bp->b", ma @ pa.T, ma)
+    return ref, 0.5 * ulp(ref, "fp32") + C_MAHA * P * U64 * terms * 1.01
+
+
+def maha_case(P: int, C: int, B: int, where: str, pkind: str, seed: int = 0):
+    """(feats [B, P], means [C, P], prec [P, P]) fp32 for the Mahalanobis checks.
+    pkind "asym": a well-conditioned A A^T / P + I with asymmetric perturbations (P[0, 1] += 0.01 and 1 % noise on the upper
+    triangle only); "scaled": a diagonal spanning 1e-3 .. 1e3 plus small off-diagonal noise.
+    where "far": features unrelated to any mean; "near": a class mean + 1e-2 noise; "equal": a class mean exactly; "mixed":
+    rows cycling through the three.  Row b of the near / equal kinds sits at class (C - 1 - b) % C: the last class first."""
+    rng = np.random.default_rng(seed + 7 * P + 13 * C)                # means and precision depend on (P, C, pkind) alone
+    means = (3.0 * rng.standard_normal((C, P))).astype(np.float32)
+    if pkind == "asym":
+        a = rng.standard_normal((P, P))
+        prec = a @ a.T / P + np.eye(P)
+        prec += np.triu(0.01 * rng.standard_normal((P, P)), 1)
+        prec[0, 1] += 0.01
+    else:
+        prec = np.diag(np.logspace(-3, 3, P)) + 1e-4 * rng.standard_normal((P, P))
+    prec = prec.astype(np.float32)
+    cls = (C - 1 - np.arange(B)) % C
+    rng = np.random.default_rng([seed, P, C, B])
+    far = (3.0 * rng.standard_normal((B, P))).astype(np.float32)
+    near = (means[cls] + 0.01 * rng.standard_normal((B, P))).astype(np.float32)
+    rows = {"far": far, "near": near, "equal": means[cls].copy()}
+    if where == "mixed":
+        feats = np.stack([rows[("far", "near", "equal")[b % 3]][b] for b in range(B)])
+    else:
+        feats = rows[where]
+    return np.ascontiguousarray(feats), means, prec
+
+
 # ---- split forms: one value as an fp16 pair hi + lo (split activations, split outputs, split weights) -------------------
 FP16_SAT = 65520.0    # the first |v| that rounds above 65504: what sat_report counts (common.hpp)
 U_SPLIT = 2.0 ** -22  # relative representation error of a split in fp16's normal range (split_repr)

@@ -375,6 +375,51 @@ def test_score_emulation_within_budget(K, T):
         assert r <= 1.0, (kind, r)
 
 
+# ---- Mahalanobis -------------------------------------------------------------------------------------------------------
+def _maha_emulate(feats, means, prec, mutation=None):
+    """maha_prepare_kernel + maha_score_kernel (score.hip): the expanded form d_c = q - W_c . f + k_c accumulated in fp64 from
+    the fp32 inputs, min over the classes, 0.5 * and one rounding to fp32.  mutation:
+      "fp32"       the expanded form accumulated in fp32
+      "symmetric"  W_c = 2 P mu_c (a symmetrised P) for P mu_c + P^T mu_c
+      "drop_last"  the last class never looked at
+      "max"        max over the classes for min"""
+    t = np.float32 if mutation == "fp32" else np.float64
+    f, mu, p = (np.asarray(a, t) for a in (feats, means, prec))
+    if mutation == "drop_last":
+        mu = mu[:-1]
+    pm = mu @ p.T                                              # rows (P mu_c)^T
+    w = 2 * pm if mutation == "symmetric" else pm + mu @ p     # + (P^T mu_c)^T
+    k = np.einsum("cp,cp->c", mu, pm)
+    q = np.einsum("bp,bp->b", f @ p.T, f)
+    d = q[:, None] - f @ w.T + k[None, :]
+    m = d.max(axis=1) if mutation == "max" else d.min(axis=1)
+    return _f32(0.5 * m.astype(np.float64))
+
+
+@pytest.mark.parametrize("pkind", ["asym", "scaled"])
+@pytest.mark.parametrize("P,C", [(64, 1), (64, 17), (100, 15), (512, 16), (768, 1000)])
+def test_maha_emulation_within_budget(P, C, pkind):
+    for where in ("far", "near", "equal", "mixed"):
+        feats, means, prec = eb.maha_case(P, C, 9, where, pkind)
+        ref, bud = eb.maha_budget(feats, means, prec)
+        if where == "equal":
+            assert (ref == 0.0).all()
+        r, _ = eb.worst(_maha_emulate(feats, means, prec), ref, bud)
+        assert r <= 1.0, (where, r)
+
+
+@pytest.mark.parametrize("mutation,factor", [("fp32", 1e3), ("symmetric", 1e3), ("drop_last", 1e6), ("max", 1e6)])
+def test_maha_mutations_break_the_budget(mutation, factor):
+    """Features within 1e-2 of a class mean (row 0 at the LAST of 17 classes, a count that is no multiple of the kernel's 16
+    waves), P with an asymmetric perturbation: each mistake misses the budget by at least `factor`."""
+    feats, means, prec = eb.maha_case(64, 17, 9, "near", "asym")
+    ref, bud = eb.maha_budget(feats, means, prec)
+    assert eb.worst(_maha_emulate(feats, means, prec), ref, bud)[0] <= 1.0
+    r, _ = eb.worst(_maha_emulate(feats, means, prec, mutation), ref, bud)
+    print(f"MUTATION maha {mutation}: ratio {r:.3g}")
+    assert r > factor, (mutation, r)
+
+
 # ---- split forms -------------------------------------------------------------------------------------------------------
 def _mm(a, b):
     """a @ b.T in torch's fp32 (an MFMA pass: exact products, fp32 accumulation)."""
