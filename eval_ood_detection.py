@@ -1,6 +1,6 @@
 """eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
 and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`).
+`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`).
 
 Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
 set) → AUROC / AUPR / FPR95 → log + CSV.
@@ -102,7 +102,21 @@ def process_args(argv=None):
                         "the persistent grid on this device (mcm_amd.config.ClipGeometry.full_round_batches; ViT-B/16 on 256 CUs: "
                         "512 -> 665, +2.6 ... 3.2 %% images/sec; ViT-L/14: 256 -> 318; the chosen batch, or that there is none, is logged).  "
                         "Scores do not depend on the batch they were computed in")
+    p.add_argument("--predict", nargs="?", type=int, const=5, default=0, metavar="K",
+                   help="also return the K (1..8; 5 when given without a value) best-matching concepts of every image and their "
+                        "softmax probabilities, from the same fused launch as the score: the ID set's top-1 / top-min(5,K) zero-shot "
+                        "accuracy goes to the log (loader label i is taken to be concept i, as in the reference's loaders) and every "
+                        "set's idx / prob / scores / labels to predictions_<set>.npz in the log directory (rank 0 under torchrun).  "
+                        "Threshold refinement keeps working and patches the SCORES only: predictions are those of the arm that "
+                        "scored the image first, so for the few hundred re-scored images prob[:,0] and -score differ in their last "
+                        "bits.  Not available with --score maha")
     args = p.parse_args(argv)
+    if args.predict:
+        if args.score == "maha":
+            p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the Mahalanobis "
+                    "baseline (--score maha) has no prompt bank to match against")
+        if not 1 <= args.predict <= 8:
+            p.error("--predict K: K must be 1..8")
     if args.decoder:
         os.environ["MCM_GPU_JPEG"] = "1" if args.decoder == "device" else "0"
     if args.templates:
@@ -175,6 +189,27 @@ def _note_pillow_files(net, sources, what, log):
         if total - seen:
             log.debug(f"{what}: {total - seen} file(s) decoded by Pillow (not taken by the device JPEG route)")
     net.__dict__["_pillow_files_seen"] = total
+
+
+def _score_set(args, net, loader, test_labels, what, log, rank, on_dev, in_dist=False):
+    """Scores of one set — `get_ood_scores_clip`, or with --predict `get_ood_predictions_clip`: the same scores, plus the
+    set's predictions written to predictions_<what>.npz (rank 0) and, for the ID set, the zero-shot accuracy line."""
+    if not args.predict:
+        return get_ood_scores_clip(args, net, loader, test_labels, in_dist=in_dist, device_out=on_dev)
+    from mcm_amd.detection import get_ood_predictions_clip, zero_shot_accuracy
+
+    scores, idx, prob, labels = get_ood_predictions_clip(args, net, loader, test_labels, topk=args.predict, device_out=True)
+    if rank == 0:
+        idx_h, labels_h = idx.cpu().numpy(), labels.cpu().numpy()
+        np.savez(os.path.join(args.log_directory, f"predictions_{what}.npz"), idx=idx_h, prob=prob.cpu().numpy(),
+                 scores=scores.cpu().numpy(), labels=labels_h)
+        if in_dist:
+            k5 = min(5, args.predict)
+            acc = zero_shot_accuracy(idx_h, labels_h, ks=(1, k5))
+            log.debug(f"zero-shot ID accuracy: top-1 {100 * acc[1]:.2f} %, top-{k5} {100 * acc[k5]:.2f} % over {len(labels_h)} images "
+                      "(loader label i is taken to be concept i, as in the reference's loaders)"
+                      + ("" if args.weights else " — seeded synthetic weights: a plumbing check, not an accuracy"))
+    return scores if on_dev else scores.cpu().numpy().astype(np.float32, copy=False)
 
 
 def main(argv=None):
@@ -273,7 +308,7 @@ def main(argv=None):
         classwise_mean, precision = stats["classwise_mean"], stats["precision"]
         in_score = get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_dist=True)
     else:
-        in_score = get_ood_scores_clip(args, net, test_loader, test_labels, in_dist=True, device_out=on_dev)
+        in_score = _score_set(args, net, test_loader, test_labels, "id", log, rank, on_dev, in_dist=True)
         _note_pillow_files(net, sources, "id", log)
     net.warn_if_saturated(f"the ID set {args.in_dataset}")
     refiner, net32 = None, None
@@ -314,7 +349,7 @@ def main(argv=None):
         if args.score == "maha":
             out_score = get_Mahalanobis_score(args, net, ood_loader, classwise_mean, precision, in_dist=False)
         else:
-            out_score = get_ood_scores_clip(args, net, ood_loader, test_labels, device_out=on_dev)
+            out_score = _score_set(args, net, ood_loader, test_labels, out_dataset, log, rank, on_dev)
             _note_pillow_files(net, sources, out_dataset, log)
             if refiner is not None:
                 set_loaders[out_dataset] = ood_loader

@@ -38,7 +38,9 @@ extern "C" {
                           * mcm_kernel_faults + the sticky fault word (every wait of a persistent kernel is bounded)
                           * 5: mcm_config.v_hidden_act / t_hidden_act (MCM_ACT_*: the MLP activation is a property of the
                           * model; 0 = QuickGELU as before, 1 = exact erf GELU for OpenCLIP-trained checkpoints) and the
-                          * MCM_LINEAR_ACT_GELU flag of mcm_op_linear_ex */
+                          * MCM_LINEAR_ACT_GELU flag of mcm_op_linear_ex
+                          * (still 5) mcm_score_features_topk / mcm_score_topk: two added symbols, no struct, constant or
+                          * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged */
 
 /* error codes */
 #define MCM_OK 0
@@ -190,6 +192,35 @@ int mcm_score_features(mcm_handle* h, const float* img_feat_dev, int32_t B,
  * loop; the reference re-encodes it every batch with identical results). */
 int mcm_score(mcm_handle* h, const float* pixels_dev, int32_t B, const float* text_feat_dev,
               int32_t K, float T, int32_t kind, float* scores_dev, void* stream);
+
+/* ---- top-k matched concepts next to every score (added under ABI 5: symbols only) ---------------------------------
+ * Replaces what a consumer of the reference does with the [B,K] softmax it pulls to the host
+ * (utils/detection_util.py:232-236: `output = image_features @ text_features.T`, `smax = softmax(output / T)`)
+ * to learn WHICH concept an image matched — np.argmax / argsort of smax per row, the zero-shot prediction the MCM
+ * paper reports top-1 / top-5 accuracy of.  The same single launch as mcm_score_features; [B,K] still never
+ * reaches HBM, and scores_dev receives the bits mcm_score_features writes for the same arguments.
+ *   idx_dev  int32 [B, topk]: the bank rows of the topk largest similarities, 1 <= topk <= MCM_TOPK_MAX, ordered by
+ *            value descending, then by row index ascending — numpy.argsort(-sim, kind="stable")[:topk].
+ *            Ties: equal similarities (+0.0 and -0.0 are equal) go to the lower index first.
+ *            NaN: a NaN similarity is never selected.  A slot with no candidate left (topk > K, or fewer than topk
+ *            non-NaN similarities) holds -1.
+ *   prob_dev fp32 [B, topk] or NULL: softmax(sim / T)[idx] from the exp terms and the fp64 normaliser of the score
+ *            itself, for EVERY kind (MCM_SCORE_MAX_LOGIT then runs the softmax it otherwise skips).  For
+ *            MCM_SCORE_MCM on a NaN-free row prob[b,0] == -scores[b] bit for bit.  NaN where idx is -1.
+ * Refusals (nothing is launched): MCM_EINVAL for topk outside 1..MCM_TOPK_MAX, a NULL scores_dev / idx_dev, T <= 0,
+ * a bad B / K / kind, and the sizes mcm_score_features refuses (proj_dim % 4, (proj_dim + K) * 4 > 150 KiB).
+ *
+ * mcm_score_topk is one batch of the hot loop body with it (mcm_score / mcm_score_u8 / mcm_score_x2 in one entry):
+ * pixel_format is MCM_PIXELS_*; x2 != 0 runs the split-activation arm under the rules of mcm_score_x2 (fp16 handle with
+ * the workspace, B <= the arm's largest batch — otherwise MCM_EINVAL / MCM_ERANGE), x2 == 0 the handle's own arm through
+ * the encode calls of mcm_score / mcm_score_u8.  Asynchronous on `stream`, no allocation, graph-capturable. */
+#define MCM_TOPK_MAX 8
+int mcm_score_features_topk(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev,
+                            int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev,
+                            int32_t* idx_dev /* [B,topk] */, float* prob_dev /* [B,topk] or NULL */, void* stream);
+int mcm_score_topk(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t x2, int32_t B,
+                   const float* text_feat_dev, int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev,
+                   int32_t* idx_dev, float* prob_dev, void* stream);
 
 /* uint8 ingest: pixels_dev is uint8 NHWC [B,image_size,image_size,3] (what a
  * JPEG decoder + resize/crop produces); ToTensor (/255) and Normalize with the CLIP mean/std of

@@ -421,6 +421,11 @@ hipError_t launch_maha_score(const float* feats, int B, const float* prec, const
 
 hipError_t launch_score(const float* img, int B, const float* text, int K, int P, float T,
                         int kind, float* scores, hipStream_t s);
+// the top-k form of the same tail (score_kernel<true>): idx [B,topk] int32, prob [B,topk] fp32 or nullptr;
+// score_shape_ok: the size rules both launches refuse by (P % 4, (P + K) * 4 <= 150 KiB of LDS)
+bool score_shape_ok(int K, int P);
+hipError_t launch_score_topk(const float* img, int B, const float* text, int K, int P, float T, int kind,
+                             int topk, float* scores, int* idx, float* prob, hipStream_t s);
 
 // metrics.hip: AUROC / AUPR / FPR@recall of two device score vectors; results land in the first
 // 4 doubles of `workspace` (>= measures_workspace_bytes(n_pos + n_neg)), *out_dev points at them

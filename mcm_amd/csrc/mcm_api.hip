@@ -1312,6 +1312,47 @@ int mcm_score(mcm_handle* h, const float* pixels_dev, int32_t B, const float* te
   return mcm_score_features(h, h->feat, B, text_feat_dev, K, T, kind, scores_dev, stream);
 }
 
+namespace {
+// every refusal of the top-k tail, made before anything is launched (mcm_score_topk encodes first)
+int check_topk_call(mcm_handle* h, const float* text_feat_dev, int32_t B, int32_t K, float T, int32_t kind,
+                    int32_t topk, const float* scores_dev, const int32_t* idx_dev) {
+  if (!text_feat_dev || !scores_dev || !idx_dev) return fail(h, MCM_EINVAL, "null pointer");
+  if (B <= 0 || K <= 0 || kind < 0 || kind > MCM_SCORE_VAR || !(T > 0.f))
+    return fail(h, MCM_EINVAL, "bad B / K / kind / T");
+  if (topk < 1 || topk > MCM_TOPK_MAX) return fail(h, MCM_EINVAL, "topk must be 1..MCM_TOPK_MAX");
+  if (!score_shape_ok(K, h->cfg.proj_dim))
+    return fail(h, MCM_EINVAL, "proj_dim % 4 != 0, or the bank exceeds the scoring tail's LDS ((proj_dim + K) * 4 > 150 KiB)");
+  return MCM_OK;
+}
+}  // namespace
+
+int mcm_score_features_topk(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev,
+                            int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev, int32_t* idx_dev,
+                            float* prob_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!img_feat_dev) return fail(h, MCM_EINVAL, "null pointer");
+  int rc = check_topk_call(h, text_feat_dev, B, K, T, kind, topk, scores_dev, idx_dev);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * (double)K * h->cfg.proj_dim);
+  HIP_TRY(h, launch_score_topk(img_feat_dev, B, text_feat_dev, K, h->cfg.proj_dim, T, kind, topk, scores_dev,
+                               idx_dev, prob_dev, s));
+  return MCM_OK;
+}
+
+int mcm_score_topk(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t x2, int32_t B,
+                   const float* text_feat_dev, int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev,
+                   int32_t* idx_dev, float* prob_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC)
+    return fail(h, MCM_EINVAL, "unknown pixel_format");
+  int rc = check_topk_call(h, text_feat_dev, B, K, T, kind, topk, scores_dev, idx_dev);
+  if (rc) return rc;
+  if ((rc = encode_image_impl(h, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, h->feat, stream, true, x2 != 0)))
+    return rc;
+  return mcm_score_features_topk(h, h->feat, B, text_feat_dev, K, T, kind, topk, scores_dev, idx_dev, prob_dev, stream);
+}
+
 int mcm_saturation_check(mcm_handle* h, int32_t on) {
   if (!h) return MCM_EINVAL;
   h->sat_on = on != 0;

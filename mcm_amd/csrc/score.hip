@@ -14,6 +14,11 @@
 // coalesced 1-KiB wave reads (a wave owns a prompt, lanes split the feature dim).
 // All arithmetic fp32 with fp64 block reductions (the sums of K terms), independent of the
 // towers' MFMA precision mode.
+//
+// score_kernel<true> (mcm_score_features_topk) additionally answers WHICH concepts matched: the
+// reference leaves that to `np.argmax(smax)` on the [B,K] copy it pulls to the host (:236); here
+// the top-k indices and their softmax probabilities come out of the same LDS row, [B,K] still
+// never reaches HBM.  score_kernel<false> is the plain tail: no run-time branch separates the two.
 #include "common.hpp"
 
 namespace {
@@ -38,9 +43,25 @@ __device__ __forceinline__ double block_sum_d(double v, double* red, int lane, i
   return t;
 }
 
+// (value, index) pairs under the selection order of the top-k form: value descending, then index
+// ascending (numpy.argsort(-sim, kind="stable")); index < 0 = no candidate.  +0.0 == -0.0, so the
+// lower index wins between them; a NaN never compares and is never a candidate.
+__device__ __forceinline__ void pair_better(float& v, int& i, float ov, int oi) {
+  if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) {
+    v = ov;
+    i = oi;
+  }
+}
+
+// TOPK: also write the `topk` best-matching bank rows of each image to idx [B,topk] and, with
+// prob != nullptr, their softmax(sim/T) to prob [B,topk] (slots without a candidate: -1 / NaN).
+// The trailing three parameters are not read by the plain instantiation.
+template <bool TOPK>
 __global__ __launch_bounds__(NWV * 64) void score_kernel(const float* __restrict__ img,
                                                     const float* __restrict__ text, int K, int P,
-                                                    float T, int kind, float* __restrict__ scores) {
+                                                    float T, int kind, float* __restrict__ scores,
+                                                    int topk, int* __restrict__ idx,
+                                                    float* __restrict__ prob) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* f = (float*)smem;        // [P]
   float* sim = f + P;             // [K]
@@ -72,9 +93,57 @@ __global__ __launch_bounds__(NWV * 64) void score_kernel(const float* __restrict
   m = redf[0];
 #pragma unroll
   for (int i = 1; i < NWV; ++i) m = fmaxf(m, redf[i]);
+  float selv = 0.f;  // thread r < topk keeps winner r: sim[] is about to be overwritten
+  int seli = -1;
+  if constexpr (TOPK) {
+    // Round r: the block-wide best entry strictly after winner r-1 in the selection order.  No
+    // masking, sim[] is left as it is; the 16-entry stage is double-buffered, one barrier a round.
+    __shared__ float stv[2][NWV];
+    __shared__ int sti[2][NWV];
+    float pv = INFINITY;
+    int pi = -1;
+    for (int r = 0; r < topk; ++r) {
+      float bv = 0.f;
+      int bi = -1;
+      for (int k = tid; k < K; k += NWV * 64) {  // k ascending: a strict > keeps the lower index
+        const float v = sim[k];
+        if ((v < pv || (v == pv && k > pi)) && (bi < 0 || v > bv)) {
+          bv = v;
+          bi = k;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        pair_better(bv, bi, ov, oi);
+      }
+      if (lane == 0) {
+        stv[r & 1][wave] = bv;
+        sti[r & 1][wave] = bi;
+      }
+      __syncthreads();
+      bv = stv[r & 1][0];
+      bi = sti[r & 1][0];
+#pragma unroll
+      for (int i = 1; i < NWV; ++i) pair_better(bv, bi, stv[r & 1][i], sti[r & 1][i]);
+      if (bi < 0) break;  // nothing left (topk > K, or NaNs): the remaining slots stay -1
+      if (tid == r) {
+        selv = bv;
+        seli = bi;
+      }
+      pv = bv;
+      pi = bi;
+    }
+    if (tid < topk) idx[(size_t)b * topk + tid] = seli;
+  }
   if (kind == MCM_SCORE_MAX_LOGIT) {
     if (tid == 0) scores[b] = -m;
-    return;
+    if constexpr (TOPK) {
+      if (!prob) return;  // with probabilities the softmax below still runs
+    } else {
+      return;
+    }
   }
   const float mt = m / T;
   double z = 0.0, ez = 0.0;
@@ -86,6 +155,13 @@ __global__ __launch_bounds__(NWV * 64) void score_kernel(const float* __restrict
     ez += (double)e * (double)u;
   }
   z = block_sum_d(z, red, lane, wave);
+  if constexpr (TOPK) {
+    // the same expf(sim/T - max/T) term and the same fp64 z as the score: for MCM on a NaN-free
+    // row prob[b,0] = (float)(1.0 / z) = -scores[b], bit for bit
+    if (prob && tid < topk)
+      prob[(size_t)b * topk + tid] = seli < 0 ? NAN : (float)((double)expf(selv / T - mt) / z);
+    if (kind == MCM_SCORE_MAX_LOGIT) return;
+  }
   if (kind == MCM_SCORE_MCM) {
     if (tid == 0) scores[b] = -(float)(1.0 / z);          // max softmax = exp(0)/z
   } else if (kind == MCM_SCORE_ENERGY) {
@@ -205,11 +281,32 @@ hipError_t launch_score(const float* img, int B, const float* text, int K, int P
   if (lds > 150 * 1024) return hipErrorInvalidValue;
   static PerDeviceFlag attr_set;
   if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)score_kernel,
+    hipError_t e = hipFuncSetAttribute((const void*)score_kernel<false>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     if (e != hipSuccess) return e;
     attr_set.set();
   }
-  hipLaunchKernelGGL(score_kernel, dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores);
+  hipLaunchKernelGGL(score_kernel<false>, dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores,
+                     0, (int*)nullptr, (float*)nullptr);
+  return hipGetLastError();
+}
+
+bool score_shape_ok(int K, int P) { return K > 0 && P > 0 && P % 4 == 0 && (int64_t)(P + (int64_t)K) * 4 <= 150 * 1024; }
+
+hipError_t launch_score_topk(const float* img, int B, const float* text, int K, int P, float T, int kind,
+                             int topk, float* scores, int* idx, float* prob, hipStream_t s) {
+  if (B <= 0 || !score_shape_ok(K, P) || kind < 0 || kind > MCM_SCORE_VAR || !(T > 0.f) || topk < 1 ||
+      topk > MCM_TOPK_MAX || !scores || !idx)
+    return hipErrorInvalidValue;
+  const int lds = (P + K) * (int)sizeof(float);
+  static PerDeviceFlag attr_set;
+  if (!attr_set.get()) {
+    hipError_t e = hipFuncSetAttribute((const void*)score_kernel<true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return e;
+    attr_set.set();
+  }
+  hipLaunchKernelGGL(score_kernel<true>, dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores,
+                     topk, idx, prob);
   return hipGetLastError();
 }

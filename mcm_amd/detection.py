@@ -174,6 +174,72 @@ def get_ood_scores_clip(args, net, loader, test_labels, in_dist=False, device_ou
     return full.detach().cpu().numpy().astype(np.float32, copy=False)[:n_total].copy()
 
 
+def get_ood_predictions_clip(args, net, loader, test_labels, topk=5, device_out=False):
+    """`get_ood_scores_clip` that also says which concepts every sample matched: the zero-shot prediction a consumer of
+    the reference takes from the [b,K] softmax it copies to the host every batch (utils/detection_util.py:232-236), here
+    from the same fused launch that writes the score (`net.score_images(..., topk=)`), so [b,K] still never exists.
+
+    Same prompt-bank cache, same contiguous per-rank shards and same sample order as `get_ood_scores_clip`.  Returns
+    `(scores [n] fp32, idx [n,topk] int32, prob [n,topk] fp32, labels [n] int64)`: the scores `get_ood_scores_clip`
+    returns, the bank rows of the topk largest similarities per sample (best first, ties to the lower row, -1 where
+    nothing is left), their softmax(sim / T), and the loader's own labels in the same order — ndarrays, or device
+    tensors with `device_out=True`.  Under world_size > 1 the four arrays are all-gathered to every rank; the loader
+    must then be one `shard_loader` can split by sample index."""
+    import torch
+
+    if getattr(args, "model", "CLIP") != "CLIP":
+        raise ValueError(f"unsupported --model {args.model!r} (the reference only defines CLIP)")
+    if args.score not in SCORE_KINDS:
+        raise ValueError(f"unsupported --score {args.score!r} for get_ood_predictions_clip")
+    if not hasattr(net, "score_images"):
+        raise TypeError("net must be a mcm_amd NativeCLIP (fused score_images path); there is no eager fallback")
+    topk = int(topk)
+    rank, ws = mdist.world()
+    n_total = len(loader.dataset)
+    with torch.no_grad():
+        text_features = prompt_bank(args, net, test_labels)
+        dev = text_features.device
+        batches = loader
+        if ws > 1:
+            lo, hi = mdist.shard_range(n_total, rank, ws)
+            batches = shard_loader(loader, lo, hi)
+            if batches is None:
+                raise TypeError("get_ood_predictions_clip under world_size > 1 needs a loader with .shard(lo, hi) or a "
+                                "torch DataLoader over a map-style dataset")
+        parts = ([], [], [], [])
+        for images, labels in batches:
+            s, i, p = net.score_images(images, text_features, float(args.T), args.score, topk=topk)
+            for dst, t in zip(parts, (s, i, p, torch.as_tensor(labels).reshape(-1).to(device=dev, dtype=torch.int64))):
+                dst.append(t)
+        empty = (torch.empty(0, dtype=torch.float32, device=dev), torch.empty((0, topk), dtype=torch.int32, device=dev),
+                 torch.empty((0, topk), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+        full = [torch.cat(p) if p else e for p, e in zip(parts, empty)]
+        if mdist.group_active():
+            full = [mdist.all_gather_rows(t, n_total) for t in full]
+    full = [t.detach()[:n_total] for t in full]
+    if device_out:
+        return tuple(full)
+    return tuple(t.cpu().numpy().copy() for t in full)
+
+
+def zero_shot_accuracy(idx, labels, ks=(1, 5)):
+    """Top-k zero-shot accuracy from `get_ood_predictions_clip`'s `idx` [n,topk] and `labels` [n]: {k: fraction of the
+    samples whose label is among their first k indices}.  A -1 slot (no candidate) never matches; a k beyond the topk
+    the indices were computed with cannot be answered and raises."""
+    idx = np.asarray(idx.detach().cpu() if hasattr(idx, "detach") else idx)
+    labels = np.asarray(labels.detach().cpu() if hasattr(labels, "detach") else labels).reshape(-1)
+    if idx.ndim != 2 or idx.shape[0] != labels.shape[0]:
+        raise ValueError(f"idx must be [n,topk] and labels [n], got {idx.shape} and {labels.shape}")
+    out = {}
+    for k in ks:
+        if not 1 <= int(k) <= idx.shape[1]:
+            raise ValueError(f"top-{k} accuracy needs 1 <= k <= topk = {idx.shape[1]}")
+        first = idx[:, :int(k)].astype(np.int64)
+        hit = ((first == labels.astype(np.int64)[:, None]) & (first >= 0)).any(axis=1)
+        out[int(k)] = float(hit.mean()) if hit.size else float("nan")
+    return out
+
+
 def shard_loader(loader, lo: int, hi: int):
     """A loader over samples [lo, hi) of `loader.dataset`, in order — a rank's shard BEFORE any decode happens.
     The build's own loaders have `.shard`; a torch-style DataLoader (map-style `dataset`, `batch_size`, the reference's

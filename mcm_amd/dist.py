@@ -136,6 +136,32 @@ def all_gather_scores(local, n_total: int):
     return torch.cat(parts).to(home)
 
 
+def all_gather_rows(local, n_total: int):
+    """`all_gather_scores` for rows of any dtype: `local` [n_local, ...] holds this rank's contiguous `shard_range`
+    shard of n_total rows (labels, top-k indices, probabilities); every rank gets [n_total, ...] in dataset order, dtype
+    kept.  A device tensor under gloo (ranks sharing a device: logic checks) takes the same host bounce."""
+    import torch
+    import torch.distributed as dist
+
+    rank, ws = world()
+    if not group_active():
+        return local
+    home = local.device
+    if dist.get_backend() == "gloo" and local.is_cuda:
+        local = local.cpu()
+    per = -(-n_total // ws)
+    tail = tuple(local.shape[1:])
+    buf = torch.zeros((per,) + tail, dtype=local.dtype, device=local.device)
+    buf[: local.shape[0]] = local
+    out = torch.empty((ws * per,) + tail, dtype=local.dtype, device=local.device)
+    dist.all_gather_into_tensor(out, buf)
+    parts = []
+    for r in range(ws):
+        lo, hi = shard_range(n_total, r, ws)
+        parts.append(out[r * per: r * per + (hi - lo)])
+    return torch.cat(parts).to(home)
+
+
 def all_reduce_sum(t):
     """Sum of a float tensor over the ranks, in place, on every rank (a no-op without a process group).  Device tensors go
     over RCCL; under gloo (ranks sharing a device: logic checks) a device tensor takes a host bounce."""

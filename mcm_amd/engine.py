@@ -33,6 +33,8 @@ HARNESS_LIB_PATH = os.path.join(_HERE, "libmcm_hip_harness.so")
 KERNEL_CLASSES = ["patchify", "gemm", "layernorm", "attention", "pool_project", "score", "embed",
                   "gemm_qkv", "gemm_outproj", "gemm_fc1", "gemm_fc2"]  # gemm_*: sub-classes of "gemm" (MCM_KC_GEMM_*)
 
+TOPK_MAX = 8  # include/mcm.h MCM_TOPK_MAX: concepts the top-k scoring tail returns per image
+
 _libs = {}
 
 
@@ -74,6 +76,8 @@ def load_library(harness: bool = False):
     L.mcm_encode_image.argtypes = [vp, vp, i32, vp, vp]
     L.mcm_score_features.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
     L.mcm_score.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
+    L.mcm_score_features_topk.argtypes = [vp, vp, i32, vp, i32, f32, i32, i32, vp, vp, vp, vp]
+    L.mcm_score_topk.argtypes = [vp, vp, i32, i32, i32, vp, i32, f32, i32, i32, vp, vp, vp, vp]
     L.mcm_profile_enable.argtypes = [vp, i32]
     L.mcm_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
@@ -165,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "mcm_jpeg_entropy_decode", "mcm_jpeg_reconstruct",
     "mcm_x2_max_batch", "mcm_encode_image_x2", "mcm_score_x2", "mcm_op_layernorm_split", "mcm_op_attention_split",
     "mcm_kernel_faults",
+    "mcm_score_features_topk", "mcm_score_topk",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -352,26 +357,67 @@ class NativeCLIP:
             raise ValueError(f"text_features must be [K,{self.geo.proj_dim}], got {tuple(t.shape)}")
         return t
 
-    def score_features(self, image_features, text_features, T: float = 1.0, score: str = "MCM"):
+    def _topk_out(self, b: int, topk: int):
+        """(scores [b] fp32, idx [b,topk] int32, prob [b,topk] fp32) on the device for the top-k tail."""
+        import torch
+
+        if not 1 <= int(topk) <= TOPK_MAX:
+            raise ValueError(f"topk must be 1..{TOPK_MAX} (0: scores only), got {topk}")
+        return (torch.empty(b, device=self.device, dtype=torch.float32),
+                torch.empty((b, int(topk)), device=self.device, dtype=torch.int32),
+                torch.empty((b, int(topk)), device=self.device, dtype=torch.float32))
+
+    def _score_images_topk(self, pixel_values, text_features, T, score, topk, x2: bool):
+        """`score_images` / `score_images_x2` with the top-k tail (mcm_score_topk), in chunks of the arm's largest batch."""
+        import torch
+
+        nb = self.x2_max_batch if x2 else self.max_batch
+        if nb <= 0:
+            raise RuntimeError("the split-activation arm needs an fp16 handle")
+        px = self._pixels(pixel_values)
+        fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
+        t = self._bank(text_features)
+        out, idx, prob = self._topk_out(px.shape[0], topk)
+        for s in range(0, px.shape[0], nb):
+            n = min(nb, px.shape[0] - s)
+            self._check(self._lib.mcm_score_topk(self._h, px[s:s + n].data_ptr(), fmt, int(x2), n, t.data_ptr(), t.shape[0],
+                                                 float(T), SCORE_KINDS[score], int(topk), out[s:s + n].data_ptr(),
+                                                 idx[s:s + n].data_ptr(), prob[s:s + n].data_ptr(), _stream_ptr()))
+        return out, idx, prob
+
+    def score_features(self, image_features, text_features, T: float = 1.0, score: str = "MCM", topk: int = 0):
+        """features [b,P] + bank [K,P] → scores [b] fp32 on the device.  `topk` > 0 (at most 8): also which concepts
+        matched — returns (scores, idx [b,topk] int32, prob [b,topk] fp32): the bank rows of the topk largest
+        similarities (value descending, ties to the lower row, NaN never, -1 where nothing is left) and their
+        softmax(sim / T); the scores are the bits of the `topk=0` call (include/mcm.h mcm_score_features_topk)."""
         import torch
 
         f = image_features.to(device=self.device, dtype=torch.float32).contiguous()
         if f.dim() != 2 or f.shape[1] != self.geo.proj_dim:
             raise ValueError(f"image_features must be [b,{self.geo.proj_dim}], got {tuple(f.shape)}")
         t = self._bank(text_features)
+        if topk:
+            out, idx, prob = self._topk_out(f.shape[0], topk)
+            self._check(self._lib.mcm_score_features_topk(self._h, f.data_ptr(), f.shape[0], t.data_ptr(), t.shape[0],
+                                                          float(T), SCORE_KINDS[score], int(topk), out.data_ptr(),
+                                                          idx.data_ptr(), prob.data_ptr(), _stream_ptr()))
+            return out, idx, prob
         out = torch.empty(f.shape[0], device=self.device, dtype=torch.float32)
         self._check(self._lib.mcm_score_features(self._h, f.data_ptr(), f.shape[0], t.data_ptr(),
                                                  t.shape[0], float(T), SCORE_KINDS[score],
                                                  out.data_ptr(), _stream_ptr()))
         return out
 
-    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None):
+    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
         """pixels [b,3,S,S] + pre-encoded bank [K,P] → scores [b] fp32 on device (one
-        iteration of the reference loop, utils/detection_util.py:223-248)."""
+        iteration of the reference loop, utils/detection_util.py:223-248).  `topk` > 0: (scores, idx, prob) as
+        `score_features` returns them (`out` is not used then)."""
         import torch
 
         if self.x2_default:
-            return self.score_images_x2(pixel_values, text_features, T, score, out=out)
+            return self.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk)
+        if topk:
+            return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=False)
         px = self._pixels(pixel_values)
         fn = self._lib.mcm_score_u8 if px.dtype == torch.uint8 else self._lib.mcm_score
         t = self._bank(text_features)
@@ -394,12 +440,14 @@ class NativeCLIP:
         """Non-zero when a persistent kernel gave up a bounded wait (include/mcm.h mcm_kernel_faults): 0 in every correct run."""
         return int(self._lib.mcm_kernel_faults(self._h))
 
-    def score_images_x2(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None):
+    def score_images_x2(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
         """`score_images` through the split-activation arm: the same weights and workspace, every MFMA operand activation as a
         hi + lo pair of fp16 numbers — scores that agree with the exact-fp32 arm to fp32 round-off, at several times its
-        speed.  Any number of images (chunks of `x2_max_batch`)."""
+        speed.  Any number of images (chunks of `x2_max_batch`).  `topk` > 0: (scores, idx, prob), as `score_images`."""
         import torch
 
+        if topk:
+            return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=True)
         nb = self.x2_max_batch
         if nb <= 0:
             raise RuntimeError("the split-activation arm needs an fp16 handle")
@@ -560,8 +608,8 @@ class _X2Scorer:
         self.net, self.device, self.geo = net, net.device, net.geo
         self.max_batch = net.x2_max_batch
 
-    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None):
-        return self.net.score_images_x2(pixel_values, text_features, T, score, out=out)
+    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
+        return self.net.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk)
 
 
 class GraphedScorer:
