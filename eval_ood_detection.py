@@ -1,6 +1,6 @@
 """eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
 and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`).
+`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`).
 
 Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
 set) → AUROC / AUPR / FPR95 → log + CSV.
@@ -110,7 +110,14 @@ def process_args(argv=None):
                         "Threshold refinement keeps working and patches the SCORES only: predictions are those of the arm that "
                         "scored the image first, so for the few hundred re-scored images prob[:,0] and -score differ in their last "
                         "bits.  Not available with --score maha")
+    p.add_argument("--maha-fit", default="host", choices=["host", "device"],
+                   help="how --score maha fits its statistics: host (the reference's recipe: every training feature copied to the "
+                        "host, torch.cov in float64 there, on rank 0 only under torchrun) or device (running fp64 sums in HBM, one "
+                        "kernel per batch, every rank fitting its own shard of the training set and one all-reduce at the end; "
+                        "same class means bit for bit, the covariance within its fp64 error budget)")
     args = p.parse_args(argv)
+    if args.maha_fit == "device" and args.score != "maha":
+        p.error("--maha-fit device needs --score maha (no other score fits anything)")
     if args.predict:
         if args.score == "maha":
             p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the Mahalanobis "
@@ -279,12 +286,19 @@ def main(argv=None):
     if args.score == "maha":  # reference eval_ood_detection.py:72-79
         args.feat_dim = net.geo.proj_dim
         os.makedirs(args.template_dir, exist_ok=True)
-        # world_size > 1: the fit (a host-side float64 step over the training features) runs on rank 0 only; the two
-        # statistics are broadcast (RCCL) and every rank scores its own shard of each test set (get_Mahalanobis_score)
-        if args.generate and rank == 0:
+        # world_size > 1: the host fit (a host-side float64 step over the training features) runs on rank 0 only; with
+        # --maha-fit device every rank fits its shard of the training set and the running sums are all-reduced (rank 0 writes
+        # the files).  Either way the two statistics are then broadcast (RCCL) and every rank scores its own shard of each
+        # test set (get_Mahalanobis_score)
+        if args.generate and (rank == 0 or args.maha_fit == "device"):
             n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
             train_loader = _loader(args, net, "train", n_train, False, sources)
-            get_mean_prec(args, net, train_loader)
+            if args.maha_fit == "device":
+                from mcm_amd.detection import get_mean_prec_device
+
+                get_mean_prec_device(args, net, train_loader)
+            else:
+                get_mean_prec(args, net, train_loader)
         # like the reference (:77-78) the statistics are always read back from the files get_mean_prec wrote —
         # or that an earlier run wrote, which is what `--generate ""` (argparse's only falsy bool) is for
         stats = {"classwise_mean": torch.empty((args.n_cls, args.feat_dim)), "precision": torch.empty((args.feat_dim, args.feat_dim))}

@@ -40,7 +40,8 @@ extern "C" {
                           * model; 0 = QuickGELU as before, 1 = exact erf GELU for OpenCLIP-trained checkpoints) and the
                           * MCM_LINEAR_ACT_GELU flag of mcm_op_linear_ex
                           * (still 5) mcm_score_features_topk / mcm_score_topk: two added symbols, no struct, constant or
-                          * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged */
+                          * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged
+                          * (still 5) mcm_maha_fit_accumulate: an added symbol, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -350,6 +351,21 @@ int mcm_maha_prepare(mcm_handle* h, const float* means_dev, const float* prec_de
                      double* w_dev, double* k_dev, void* stream);
 int mcm_maha_score_features(mcm_handle* h, const float* feats_dev, int32_t B, const float* prec_dev,
                             const double* w_dev, const double* k_dev, int32_t C, float* scores_dev,
+                            void* stream);
+/* The fit's running statistics (added under ABI 5: a symbol only), what get_mean_prec's covariance needs from a stream
+ * of feature batches.  With x_b = (double)feats_dev[b] - (double)shift_dev (shift_dev [proj_dim] fp32, NULL = 0):
+ *   gram_dev [proj_dim, proj_dim] += sum_b x_b x_b^T        sum_dev [proj_dim] += sum_b x_b        (fp64, b < B)
+ * gram_dev and sum_dev are the caller's, zeroed by the caller before the first batch (like w_dev / k_dev above, the
+ * library never allocates them); after n rows  cov = (gram - sum sum^T / n) / (n - 1)  whatever the shift, which is
+ * there for the error alone: a shift near the column means (the first batch's) keeps the subtraction from cancelling.
+ * Every product is rounded once (fma), an element is accumulated row after row in one thread starting from the value
+ * already there: no atomics, the same bits on every run and for every split of the rows into calls.  Only the upper
+ * triangle of gram_dev is read; the lower one is written as its mirror image, so gram[i][j] == gram[j][i] bit for bit.
+ * Asynchronous on `stream`, no allocation, graph-capturable; timed under MCM_KC_SCORE.
+ * Refusals (nothing is launched): MCM_EINVAL for a NULL feats_dev / gram_dev / sum_dev or B < 1; MCM_EHIP for a
+ * proj_dim beyond 4096, as mcm_maha_score_features. */
+int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
+                            const float* shift_dev /* [proj_dim] or NULL */, double* gram_dev, double* sum_dev,
                             void* stream);
 
 /* ---- CLIP byte-level BPE tokenizer, host side --------------------------------

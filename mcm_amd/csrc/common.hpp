@@ -418,6 +418,10 @@ hipError_t launch_maha_prepare(const float* means, const float* prec, int C, int
                                hipStream_t s);
 hipError_t launch_maha_score(const float* feats, int B, const float* prec, const double* w, const double* c,
                              int C, int P, float* scores, hipStream_t s);
+// the fit's running statistics (maha_fit_kernel): gram [P,P] += sum_b x_b x_b^T, sum [P] += sum_b x_b in fp64,
+// x_b = feats[b] - shift (shift == nullptr: 0); deterministic, gram bit-symmetric
+hipError_t launch_maha_fit(const float* feats, int B, int P, const float* shift, double* gram, double* sum,
+                           hipStream_t s);
 
 hipError_t launch_score(const float* img, int B, const float* text, int K, int P, float T,
                         int kind, float* scores, hipStream_t s);

@@ -1040,6 +1040,17 @@ int mcm_maha_score_features(mcm_handle* h, const float* feats_dev, int32_t B, co
   return MCM_OK;
 }
 
+int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev, int32_t B, const float* shift_dev,
+                            double* gram_dev, double* sum_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!feats_dev || !gram_dev || !sum_dev || B < 1) return fail(h, MCM_EINVAL, "bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const double P = h->cfg.proj_dim;
+  Scope sc(h, s, MCM_KC_SCORE, (double)B * P * (P + 1.0));  // the upper triangle: B P (P + 1) / 2 fma
+  HIP_TRY(h, launch_maha_fit(feats_dev, B, h->cfg.proj_dim, shift_dev, gram_dev, sum_dev, s));
+  return MCM_OK;
+}
+
 int mcm_encode_image_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, float* out_dev,
                         void* stream) {
   return encode_image_impl(h, pixels_dev, true, B, out_dev, stream);

@@ -256,7 +256,108 @@ __global__ __launch_bounds__(NWV * 64) void maha_score_kernel(const float* __res
   }
 }
 
+// ---- Mahalanobis fit: the running statistics of get_mean_prec on the device (mcm_maha_fit_accumulate) -------------
+// gram [P,P] += sum_b x_b x_b^T and sum [P] += sum_b x_b over the B rows of feats, x_b = (double)f_b - (double)shift.
+// The covariance is finalised on the host from (gram, sum, n); the shift (the first batch's column mean) keeps
+// gram - sum sum^T / n from cancelling when the features sit far from the origin.
+// One workgroup owns one FT x FT tile of the UPPER triangle of gram and walks all B rows, so an element's value is the
+// recurrence acc = fma(x_bi, x_bj, acc) over b in row order, started from the value gram already holds: no atomics, no
+// split of the B loop, and the same bits whether the rows arrive in one call or in several.  The tile's mirror image
+// is written from the same accumulators (gram[j][i] = gram[i][j] bit for bit; what the caller held in the lower
+// triangle is overwritten).  The workgroups of the diagonal tiles also carry their FT elements of sum, row by row.
+// A thread accumulates a 4 x 4 set of elements, rows ty + 16 r and columns tx + 16 c of the tile: the 16 lanes of a row
+// read 16 consecutive doubles of a staged feature row (no bank conflicts), the row operand is a broadcast.
+constexpr int FT = 64;  // tile edge
+constexpr int FK = 32;  // feature rows staged per step: 2 panels x FK x FT doubles = 32 KiB of LDS
+
+__global__ __launch_bounds__(256) void maha_fit_kernel(const float* __restrict__ feats, int B, int P,
+                                                       const float* __restrict__ shift, double* __restrict__ gram,
+                                                       double* __restrict__ sum) {
+  __shared__ double xs[2][FK][FT];  // the shifted rows of this step: columns of tile-row ti, of tile-column tj
+  const int nt = (P + FT - 1) / FT;
+  int idx = blockIdx.x, ti = 0;     // blockIdx.x counts the upper-triangle tiles row by row
+  while (idx >= nt - ti) {
+    idx -= nt - ti;
+    ++ti;
+  }
+  const int tj = ti + idx;
+  const bool diag = ti == tj;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  // staging: a thread converts column sc of both panels, rows sr, sr + 4, ... of the step
+  const int sc = tid & 63, sr = tid >> 6;
+  const int ci = ti * FT + sc, cj = tj * FT + sc;
+  const double shi = (shift && ci < P) ? (double)shift[ci] : 0.0;
+  const double shj = (shift && cj < P) ? (double)shift[cj] : 0.0;
+  const double(*xi)[FT] = xs[0];
+  const double(*xj)[FT] = diag ? xs[0] : xs[1];
+
+  double acc[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = ti * FT + ty + 16 * r, j = tj * FT + tx + 16 * c;
+      acc[r][c] = (i < P && j < P && i <= j) ? gram[(size_t)i * P + j] : 0.0;
+    }
+  const bool sums = diag && tid < FT;  // wave 0 of a diagonal tile: sum[ci]
+  double s = (sums && ci < P) ? sum[ci] : 0.0;
+
+  float ri[FK / 4], rj[FK / 4];
+  auto fetch = [&](int b0) {  // rows past B and columns past P read as 0 (neither is used: see the k loop, the stores)
+#pragma unroll
+    for (int m = 0; m < FK / 4; ++m) {
+      const int b = b0 + sr + 4 * m;
+      ri[m] = (b < B && ci < P) ? feats[(size_t)b * P + ci] : 0.f;
+      rj[m] = (!diag && b < B && cj < P) ? feats[(size_t)b * P + cj] : 0.f;
+    }
+  };
+  fetch(0);
+  for (int b0 = 0; b0 < B; b0 += FK) {
+    __syncthreads();  // the previous step's readers are done
+#pragma unroll
+    for (int m = 0; m < FK / 4; ++m) {
+      xs[0][sr + 4 * m][sc] = ci < P ? (double)ri[m] - shi : 0.0;
+      if (!diag) xs[1][sr + 4 * m][sc] = cj < P ? (double)rj[m] - shj : 0.0;
+    }
+    __syncthreads();
+    if (b0 + FK < B) fetch(b0 + FK);  // the next step's rows travel while this one is multiplied
+    const int kmax = min(FK, B - b0);
+    for (int k = 0; k < kmax; ++k) {
+      double a[4], b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a[r] = xi[k][ty + 16 * r];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) b[c] = xj[k][tx + 16 * c];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = fma(a[r], b[c], acc[r][c]);
+    }
+    if (sums)
+      for (int k = 0; k < kmax; ++k) s += xi[k][sc];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int i = ti * FT + ty + 16 * r, j = tj * FT + tx + 16 * c;
+      if (i < P && j < P && i <= j) {  // (a diagonal tile's lower half was computed for nothing: its mirror writes it)
+        gram[(size_t)i * P + j] = acc[r][c];
+        if (i != j) gram[(size_t)j * P + i] = acc[r][c];
+      }
+    }
+  if (sums && ci < P) sum[ci] = s;
+}
+
 }  // namespace
+
+hipError_t launch_maha_fit(const float* feats, int B, int P, const float* shift, double* gram, double* sum,
+                           hipStream_t s) {
+  if (B <= 0 || P <= 0 || P > 4096 || !feats || !gram || !sum) return hipErrorInvalidValue;
+  const int nt = (P + FT - 1) / FT;
+  hipLaunchKernelGGL(maha_fit_kernel, dim3(nt * (nt + 1) / 2), dim3(256), 0, s, feats, B, P, shift, gram, sum);
+  return hipGetLastError();
+}
 
 hipError_t launch_maha_prepare(const float* means, const float* prec, int C, int P, double* w, double* c,
                                hipStream_t s) {

@@ -306,6 +306,109 @@ def get_mean_prec(args, net, train_loader):
     return classwise_mean, precision
 
 
+def get_mean_prec_device(args, net, train_loader, return_cov=False):
+    """`get_mean_prec` as a streaming, sharded fit: the same results and files, from constant-size running statistics
+    that stay in HBM until the training set ends (`net.maha_fit_accumulate`: one fp64 kernel per batch) instead of every
+    feature on the host.  `net` must have `maha_fit_state` / `maha_fit_accumulate` (a NativeCLIP); `get_mean_prec` stays
+    the route for any other `net`.
+
+      * features: the same ops as `get_mean_prec` (`get_image_features`, then `f / f.norm()` in torch when
+        args.normalize), so the rows are the same bits;
+      * the covariance comes from gram = sum x x^T and sum = sum x of the SHIFTED rows x = f - shift, finalised on the
+        host in fp64 as (gram - sum sum^T / n) / (n - 1) and inverted by the same LAPACK call.  The shift is the fp32
+        column mean of the batch that starts at sample 0 (rank 0's first; broadcast before any rank accumulates).  It
+        does not change the covariance, only the error: without it gram - sum sum^T / n cancels for features far from
+        the origin;
+      * the reference's class-"mean" rule (`get_mean_prec`'s docstring): sample g counts into n_cb[label, g // batch_size]
+        and the feature rows g < n_batches are copied into a [n_batches, P] buffer as they stream past; the means are the
+        same fp64 `n_cb @ rows / n_c` expression on the same values: bit-equal to the host route's;
+      * world_size > 1: every rank takes `shard_range` of the training set, and gram, sum, n, the rows and the counts go
+        through one all-reduce each (sums with zeros: exact).  A loader that cannot be sharded by index is refused.
+
+    The batch size is the loader's `batch_size` (args.batch_size for a loader without one).  Returns (classwise_mean,
+    precision) on every rank, with `return_cov=True` also the fp64 covariance; rank 0 writes the two .pt files."""
+    import os
+
+    import torch
+
+    if not hasattr(net, "maha_fit_accumulate"):
+        raise TypeError("get_mean_prec_device needs a net with maha_fit_state / maha_fit_accumulate (a NativeCLIP); "
+                        "get_mean_prec is the host route")
+    rank, ws = mdist.world()
+    n_total = len(train_loader.dataset)
+    bs = int(getattr(train_loader, "batch_size", None) or args.batch_size)
+    n_batches = -(-n_total // bs)
+    batches, lo, hi = train_loader, 0, n_total
+    if ws > 1:
+        lo, hi = mdist.shard_range(n_total, rank, ws)
+        batches = shard_loader(train_loader, lo, hi)
+        if batches is None:
+            raise TypeError("--score maha under world_size > 1 needs a loader that can be sharded by index")
+
+    def features(images):
+        f = net.get_image_features(pixel_values=images).float()
+        if args.normalize:
+            f = f / f.norm(dim=-1, keepdim=True)
+        return f
+
+    n_cb = np.zeros((args.n_cls, n_batches), np.float64)
+    with torch.no_grad():
+        it = iter(batches) if hi > lo else iter(())
+        first = None
+        shift = torch.zeros(args.feat_dim, dtype=torch.float32)
+        if rank == 0 and hi > lo:  # the batch that starts at global sample 0
+            images, labels = next(it)
+            first = (features(images), labels)
+            shift = first[0].mean(dim=0)
+        mdist.broadcast_tensors([shift], src=0)
+        state = net.maha_fit_state(shift)
+        dev = state["gram"].device
+        rows = torch.zeros((n_batches, state["gram"].shape[0]), dtype=torch.float32, device=dev)
+        seen = 0
+        while seen < hi - lo:
+            if first is not None:
+                (f, labels), first = first, None
+            else:
+                try:
+                    images, labels = next(it)
+                except StopIteration:
+                    break
+                f = features(images)
+            f, g0 = f[: hi - lo - seen], lo + seen
+            b = f.shape[0]
+            net.maha_fit_accumulate(f, state)
+            if g0 < n_batches:  # the rows the reference's batch indices select
+                rows[g0: min(g0 + b, n_batches)] = f[: n_batches - g0].to(dev)
+            # labels >= n_cls are ignored, like the reference's per-class loop (:161-166) never visits them
+            lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+            lab = lab.astype(np.int64).reshape(-1)[:b]
+            keep = lab < args.n_cls
+            np.add.at(n_cb, (lab[keep], (g0 + np.arange(b)[keep]) // bs), 1.0)
+            seen += b
+        gram, fsum = state["gram"], state["sum"]
+        n_t = torch.tensor([float(state["n"])], dtype=torch.float64, device=dev)
+        ncb_t = torch.from_numpy(n_cb).to(dev)
+        for t in (gram, fsum, n_t, rows, ncb_t):
+            mdist.all_reduce_sum(t)
+    n = float(n_t.cpu()[0])
+    n_cb = ncb_t.cpu()
+    classwise_mean = ((n_cb @ rows.cpu().double()) / n_cb.sum(dim=1, keepdim=True)).float()
+    if args.normalize:
+        classwise_mean = classwise_mean / classwise_mean.norm(dim=-1, keepdim=True)
+    G, S = gram.cpu(), fsum.cpu()
+    cov = (G - torch.outer(S, S) / n) / (n - 1.0)
+    precision = torch.linalg.inv(cov).float()
+    print(f"cond number: {torch.linalg.cond(precision)}")
+    tdir = getattr(args, "template_dir", None)
+    if tdir and rank == 0:
+        os.makedirs(tdir, exist_ok=True)
+        for what, t in (("classwise_mean", classwise_mean), ("precision", precision)):
+            torch.save(t, os.path.join(tdir, maha_file_name(args, what)))
+    if return_cov:
+        return classwise_mean, precision, cov
+    return classwise_mean, precision
+
+
 def maha_file_name(args, what):
     """File names of the stored Mahalanobis statistics (reference :171-172, eval_ood_detection.py:77-78)."""
     return f"{args.model}_{what}_{args.in_dataset}_{args.max_count}_{args.normalize}.pt"

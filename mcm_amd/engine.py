@@ -145,6 +145,7 @@ def load_library(harness: bool = False):
     L.mcm_score_histogram.argtypes = [vp, vp, ctypes.c_int64, vp, i32, vp, vp]
     L.mcm_maha_prepare.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.mcm_maha_score_features.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
+    L.mcm_maha_fit_accumulate.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.mcm_measures.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, ctypes.c_double,
                                ctypes.POINTER(ctypes.c_double), vp]
     L.mcm_saturation_check.argtypes = [vp, i32]
@@ -170,6 +171,7 @@ EXPORTED_SYMBOLS = [
     "mcm_x2_max_batch", "mcm_encode_image_x2", "mcm_score_x2", "mcm_op_layernorm_split", "mcm_op_attention_split",
     "mcm_kernel_faults",
     "mcm_score_features_topk", "mcm_score_topk",
+    "mcm_maha_fit_accumulate",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -326,6 +328,32 @@ class NativeCLIP:
                                                       state["w"].data_ptr(), state["k"].data_ptr(), state["C"],
                                                       out.data_ptr(), _stream_ptr()))
         return out
+
+    def maha_fit_state(self, shift=None):
+        """Zeroed running statistics of the Mahalanobis fit: {gram [P,P] fp64, sum [P] fp64, shift [P] fp32, n}, device
+        tensors; `shift` (default 0) is subtracted from every feature row before it is accumulated (include/mcm.h
+        mcm_maha_fit_accumulate: it is there for the error, the covariance does not depend on it)."""
+        import torch
+
+        P = self.geo.proj_dim
+        sh = (torch.zeros(P, device=self.device, dtype=torch.float32) if shift is None
+              else shift.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous())
+        if sh.shape != (P,):
+            raise ValueError(f"shift must hold proj_dim = {P} values, got {tuple(sh.shape)}")
+        return {"gram": torch.zeros((P, P), device=self.device, dtype=torch.float64),
+                "sum": torch.zeros(P, device=self.device, dtype=torch.float64), "shift": sh, "n": 0}
+
+    def maha_fit_accumulate(self, features, state):
+        """features [B,P] fp32 → state: gram += sum_b x x^T, sum += sum_b x with x = f_b - shift, n += B.  One launch."""
+        import torch
+
+        f = features.to(device=self.device, dtype=torch.float32).contiguous()
+        if f.dim() != 2 or f.shape[1] != self.geo.proj_dim:
+            raise ValueError(f"features must be [B, {self.geo.proj_dim}], got {tuple(f.shape)}")
+        self._check(self._lib.mcm_maha_fit_accumulate(self._h, f.data_ptr(), f.shape[0], state["shift"].data_ptr(),
+                                                      state["gram"].data_ptr(), state["sum"].data_ptr(), _stream_ptr()))
+        state["n"] += int(f.shape[0])
+        return state
 
     def get_text_features(self, input_ids, attention_mask=None, normalize: bool = False):
         """[K,S] ids → [K,P] fp32: HF `get_text_features` (the text projection output; unit-norm rows
