@@ -36,11 +36,6 @@ struct LayerW {
   void *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;  // operand dtype
   float *bqkv = nullptr;                                               // [3D] packed
   const float *bo, *b1, *b2, *ln1w, *ln1b, *ln2w, *ln2b;               // fp32 masters
-  // LayerNorm fold (vision tower, 16-bit modes): c = W gamma and b' = b + W beta of the two GEMMs that follow a LayerNorm
-  float *cqkv = nullptr, *bqkvf = nullptr, *c1 = nullptr, *b1f = nullptr;
-  // ROW64 arm, blocked W (harness; built on first use): wo / w2 as [K-step of 32][16-row block][1 KiB piece, chunks XOR-ed] — the
-  // LDS image of a piece, contiguous in memory, so that every LDS-DMA piece is eight whole cache lines (gemm_arms.hpp ROW64)
-  void *wo_blk = nullptr, *w2_blk = nullptr;
 };
 
 struct Tower {
@@ -56,9 +51,9 @@ struct EvPair {
   int kc, kc2;  // kc2: a sub-class of kc that also gets this launch (MCM_KC_GEMM_*), -1 = none
 };
 
-}  // namespace
-
-struct mcm_handle {
+// A handle without the A/B arms' fields: mcm_handle (below, at the include of the arms) is this and nothing else in the
+// shipped library, this plus the arms' workspace in the A/B builds
+struct HandleCore {
   mcm_config cfg;
   std::map<std::string, Param> params;
   bool finalized = false;
@@ -106,17 +101,10 @@ struct mcm_handle {
   unsigned int* fault_pin = nullptr;
   unsigned int* fault_dev = nullptr;
   bool sat_on = true;
-  float2 *fold_part = nullptr, *fold_rs = nullptr;  // LayerNorm fold: row moments [v_width / 64][rows], (rstd, mean rstd) [rows]
-  // LayerNorm in the tail of the residual GEMMs (gemm.hip): per-XCD regions of counters, all zero between launches;
-  // nullptr when the device did not pass the workgroup -> XCD check (xcd_round_robin) or the widths do not qualify
-  unsigned int* ln_state = nullptr;
-  int ln_rs = 0, ln_cap8 = 0;
   std::string err;
 };
 
-namespace {
-
-int fail(mcm_handle* h, int code, const std::string& msg) {
+int fail(HandleCore* h, int code, const std::string& msg) {
   if (h) h->err = msg;
   else g_create_err = msg;
   return code;
@@ -129,7 +117,7 @@ int fail(mcm_handle* h, int code, const std::string& msg) {
       return fail(h, MCM_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
-void add_param(mcm_handle* h, const std::string& name, std::vector<int64_t> shape) {
+void add_param(HandleCore* h, const std::string& name, std::vector<int64_t> shape) {
   Param p;
   p.shape = shape;
   p.numel = 1;
@@ -137,7 +125,7 @@ void add_param(mcm_handle* h, const std::string& name, std::vector<int64_t> shap
   h->params[name] = p;
 }
 
-void add_layer_params(mcm_handle* h, const std::string& pre, int D, int ff) {
+void add_layer_params(HandleCore* h, const std::string& pre, int D, int ff) {
   for (const char* pr : {"q_proj", "k_proj", "v_proj", "out_proj"}) {
     add_param(h, pre + ".self_attn." + pr + ".weight", {D, D});
     add_param(h, pre + ".self_attn." + pr + ".bias", {D});
@@ -152,7 +140,7 @@ void add_layer_params(mcm_handle* h, const std::string& pre, int D, int ff) {
   add_param(h, pre + ".mlp.fc2.bias", {D});
 }
 
-int dev_alloc(mcm_handle* h, void** out, size_t bytes) {
+int dev_alloc(HandleCore* h, void** out, size_t bytes) {
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
   if (e != hipSuccess)
@@ -162,15 +150,15 @@ int dev_alloc(mcm_handle* h, void** out, size_t bytes) {
   return MCM_OK;
 }
 
-const float* W(mcm_handle* h, const std::string& name) { return h->params.at(name).dev; }
+const float* W(HandleCore* h, const std::string& name) { return h->params.at(name).dev; }
 
 // ---- profiling wrappers ---------------------------------------------------------------
 struct Scope {
-  mcm_handle* h;
+  HandleCore* h;
   hipStream_t s;
   int kc;
   EvPair* ev = nullptr;
-  Scope(mcm_handle* h_, hipStream_t s_, int kc_, double fl, int kc2 = -1) : h(h_), s(s_), kc(kc_) {
+  Scope(HandleCore* h_, hipStream_t s_, int kc_, double fl, int kc2 = -1) : h(h_), s(s_), kc(kc_) {
     if (!h->prof) return;
     if (h->ev_used == h->ev_pool.size()) {
       EvPair e;
@@ -198,47 +186,49 @@ struct Scope {
 // the ones still in L2 / Infinity Cache, so its consumer starts there (results do not depend on the
 // order).  `flip` alternates per launch.  Measured: LayerNorm 2.19 -> 1.99 ms per step (it reads the
 // residual stream the previous GEMM just wrote), +0.9 % end to end.
-bool next_dir(mcm_handle* h) {
+bool next_dir(HandleCore* h) {
   h->flip = !h->flip;
   return h->flip;
 }
-#ifdef MCM_HARNESS
-int g_patch_fold = 1;  // A/B (mcm_debug_patch_fold): 0 = patchify + plain patch GEMM (rounds 1 - 3), 1 = pixel-gathering patch GEMM
+// rows of a dense activation GEMM as gemm() runs it (whole 256-row tiles when the workspace has them)
+int64_t padded_rows(const HandleCore* h, int M) {
+  const int64_t mp = ((int64_t)M + 255) / 256 * 256;
+  return mp <= h->max_rows ? mp : M;
+}
+
+}  // namespace
+
+// ---- the A/B arms ---------------------------------------------------------------------
+// Everything the closed experiments need on the host (their switches, workspace, per-call planning and launches) is in
+// mcm_api_arms.hpp, which only the A/B builds include, as gemm.hip does with gemm_arms.hpp.  The shipped library has what
+// follows in its place: no arm field in the handle, the two switches shipped code reads as constants, and an `Arms` whose
+// every answer is a compile-time "no", so that each call site below folds to the shipped launches.
+#if defined(MCM_HARNESS) || defined(MCM_LN_FOLD) || defined(MCM_LN_TAIL)
+#define MCM_API_ARMS 1
+#include "mcm_api_arms.hpp"
 #else
-constexpr int g_patch_fold = 1;
+struct mcm_handle : HandleCore {};
+namespace {
+constexpr int g_patch_fold = 1, g_resize_fused_only = 0;
+struct Arms {
+  template <class... A> Arms(A&&...) {}
+  template <class... A> void consumer(A&&...) {}
+  template <class... A> static constexpr bool qkv_attention(A&&...) { return false; }
+  template <class... A> static constexpr bool resid_ln(A&&...) { return false; }
+  template <class... A> static constexpr bool column_blocks(A&&...) { return false; }
+  template <class... A> static constexpr bool skip_layernorm(A&&...) { return false; }
+  template <class... A> static constexpr int create(A&&...) { return MCM_OK; }
+  template <class... A> static constexpr int build_layer(A&&...) { return MCM_OK; }
+};
+}  // namespace
 #endif
-#ifdef MCM_HARNESS
-int g_resize_fused_only = 0;  // A/B (mcm_debug_resize_fused_only): 1 = the resize kernel's rounds-2/3 form everywhere
-#else
-constexpr int g_resize_fused_only = 0;
-#endif
-#ifdef MCM_HARNESS
-int g_nsplit = 1;  // A/B (mcm_debug_nsplit): the wide store GEMMs (QKV, fc1) as n launches over column blocks of N / n
-#endif
+
+namespace {
+
 hipError_t gemm(mcm_handle* h, hipStream_t s, int prec, int epi, const GemmArgs& a_in) {
+  hipError_t e = hipSuccess;
+  if (Arms::column_blocks(h, s, prec, epi, a_in, e)) return e;
   GemmArgs a = a_in;
-#ifdef MCM_HARNESS
-  // (N = 3 x 768 / 3 x 1024 / 3072 / 4096 only: like the other arms it does not learn ViT-H/14's 3840 / 5120 columns)
-  if (g_nsplit > 1 && (epi == EPI_STORE || epi == EPI_GELU) && a.K <= 1024 && a.N <= 4096 && a.N >= 2048 && a.N % (256 * g_nsplit) == 0 && !a.fold_rs && !a.hm && a.M > 4096) {
-    // W re-fetch experiment: the XCD's L2 (4 MiB) cannot hold all of W (fc1: 4.7 MB) beside the X
-    // panels in flight, so W streams through it once per tile round; with the columns cut in n blocks only N / n of W
-    // is live per launch (X is then read n times).  Same bits (a column's K-sum does not depend on its neighbours).
-    const int n = g_nsplit, nb = a.N / n;
-    const size_t wrow = (size_t)a.K * prec_esize(prec) * (a.ksplit ? 2 : 1);
-    hipError_t e = hipSuccess;
-    g_nsplit = 1;
-    for (int i = 0; i < n && e == hipSuccess; ++i) {
-      GemmArgs p = a_in;
-      p.N = nb;
-      p.w = (const char*)a_in.w + (size_t)i * nb * wrow;
-      p.bias = a_in.bias ? a_in.bias + (size_t)i * nb : nullptr;
-      p.out = (char*)a_in.out + (size_t)i * nb * prec_esize(prec);
-      e = gemm(h, s, prec, epi, p);
-    }
-    g_nsplit = n;
-    return e;
-  }
-#endif
   a.rev = next_dir(h) ? 1 : 0;
   a.sat = h->sat_on ? h->sat_dev : nullptr;
   // the four whole-batch shapes of an encoder layer also get a class of their own (out-proj is the HBM-bound one:
@@ -254,10 +244,8 @@ hipError_t gemm(mcm_handle* h, hipStream_t s, int prec, int epi, const GemmArgs&
   // input row only, and the pad rows' results are never read: same bits for the real rows, and batches that are not
   // multiples of 256 images (any batch at ViT-L/14's 257 tokens but 256 k; ragged last batches) get the fast kernel.
   const bool from_row0 = a.x == h->ln || a.x == h->att || a.x == h->hbuf;  // not a chunk that starts mid-buffer
-  if (epi != EPI_PATCH && from_row0 && a.M % 256 != 0 && a.N % 256 == 0 && a.ldx == a.K && a.ldo == a.N) {
-    const int64_t mp = ((int64_t)a.M + 255) / 256 * 256;
-    if (mp <= h->max_rows) a.M = (int)mp;
-  }
+  if (epi != EPI_PATCH && from_row0 && a.M % 256 != 0 && a.N % 256 == 0 && a.ldx == a.K && a.ldo == a.N)
+    a.M = (int)padded_rows(h, a.M);
   if (a.ksplit) a.K *= 2;  // the callers describe the logical problem; the split image has 2 K columns per row
   if (a.xsplit) a.ldx *= 2;           // ... and so have the rows of a split X
   if (epi_x2(epi)) a.ldo *= 2;        // ... and of a split output
@@ -269,16 +257,8 @@ hipError_t lnorm(mcm_handle* h, hipStream_t s, int prec, const float* x, const f
   if (split)
     return launch_layernorm(prec, x, g, b, y, M, D, h->cfg.ln_eps, false, s, 0, 0, next_dir(h),
                             h->sat_on ? h->sat_dev : nullptr, true);
-#ifdef MCM_HARNESS
-  // timing experiment (results are garbage): what a tower without its big LayerNorm launches would cost.
-  // MCM_ABL_SKIP_LN=1: nothing in their place; =2: a write of the 16-bit output's size (the extra epilogue store
-  // of a LayerNorm folded into the neighbouring GEMMs)
-  static const char* skip = getenv("MCM_ABL_SKIP_LN");
-  if (skip && M > 4096 && !out_f32) {
-    if (skip[0] == '2') return hipMemsetAsync(h->qkv, 0, (size_t)M * D * prec_esize(prec), s);  // dead at both LN sites
-    return hipSuccess;
-  }
-#endif
+  hipError_t e = hipSuccess;
+  if (Arms::skip_layernorm(h, s, prec, M, D, out_f32, e)) return e;
   return launch_layernorm(prec, x, g, b, y, M, D, h->cfg.ln_eps, out_f32, s, 0, 0, next_dir(h),
                           h->sat_on ? h->sat_dev : nullptr);
 }
@@ -293,85 +273,11 @@ hipError_t attn(mcm_handle* h, hipStream_t s, int prec, int nseq, int L, int hea
   return launch_attention(prec, (const char*)h->qkv + row0 * 3 * D * es, (char*)h->att + row0 * D * es, nseq, L,
                           heads, hd, causal, qrows, s, next_dir(h), hm, false, h->fault_dev);
 }
-// A/B arm (harness: mcm_debug_qkv_head_major): qkv of the 16-bit towers head-major ([3 heads][rows][64],
-// GemmArgs::hm) between the QKV projection and attention.  Bit-identical; attention 1.63 -> 1.56 ms per step, the QKV
-// projection's stores +0.04 ... 0.08 ms: no net gain, the shipped library keeps [rows][3 D].
-#ifdef MCM_HARNESS
-int g_qkv_head_major = 0;
-#else
-constexpr int g_qkv_head_major = 0;
-#endif
-#ifdef MCM_HARNESS
-int g_qkv_chunks = 1;  // A/B: QKV projection + attention per chunk of the batch (qkv of a chunk stays in the Infinity Cache)
-int g_ln_fold = 0;     // A/B: 1 = LayerNorm fold (mcm_debug_ln_fold); 0 = every LayerNorm as its own launch (shipped)
-#else
-constexpr int g_qkv_chunks = 1;
-#ifdef MCM_LN_FOLD  // A/B build of the shipped library with the fold on (make fold: libmcm_hip_fold.so, tools/bench_with_lib.py)
-constexpr int g_ln_fold = 1;
-#else
-constexpr int g_ln_fold = 0;
-#endif
-#endif
-// rows of a dense activation GEMM as gemm() runs it (whole 256-row tiles when the workspace has them)
-int64_t padded_rows(const mcm_handle* h, int M) {
-  const int64_t mp = ((int64_t)M + 255) / 256 * 256;
-  return mp <= h->max_rows ? mp : M;
-}
-hipError_t fold_stats(mcm_handle* h, hipStream_t s, int Mp, int D) {
-  Scope sc(h, s, MCM_KC_LAYERNORM, 4.0 * Mp * (D / 64));
-  return launch_fold_stats(h->fold_part, D / 64, Mp, D, h->cfg.ln_eps, h->fold_rs, s);
-}
 hipError_t lnorm_strided(mcm_handle* h, hipStream_t s, int prec, const float* x, const float* g,
                          const float* b, void* y, int M, int D, size_t xs, size_t ys, bool split = false) {
   Scope sc(h, s, MCM_KC_LAYERNORM, 8.0 * M * D);
   return launch_layernorm(prec, x, g, b, y, M, D, h->cfg.ln_eps, false, s, xs, ys, false,
                           h->sat_on ? h->sat_dev : nullptr, split);
-}
-
-// LayerNorm in the tail of the residual GEMMs (gemm.hip "LayerNorm in the tail"): 1 = the LayerNorm that follows a
-// whole-batch out-proj / fc2 of a 16-bit tower is computed by that GEMM's own waves; 0 = every LayerNorm is a launch
-// An A/B arm: bit-identical, equal at ViT-B/16 batch 512, +0.5 % at ViT-L/14, -1 ... -7 % on smaller problems
-#ifdef MCM_HARNESS
-int g_ln_tail = 0;  // mcm_debug_ln_tail
-int g_ln_cluster = 0;  // mcm_debug_ln_cluster: LayerNorm by the row panel's cluster of workgroups (gemm_arms.hpp "LNC", round 6)
-int g_ln_row = 0;      // mcm_debug_ln_row: out-proj / fc2 + the LayerNorm behind them as 64-row FULL-ROW tiles (gemm_arms.hpp ROW64, R6.7)
-int g_lnc_spin = -1;   // mcm_debug_ln_cluster_spin: < 0 the first form (wait for the partners); n >= 0 the defer form: n polls, then
-                       // the segment is left to launch_lnc_cleanup behind the GEMM
-#elif defined(MCM_LN_TAIL)  // A/B build of the shipped library with the tail on
-constexpr int g_ln_tail = 1;
-#else
-constexpr int g_ln_tail = 0;
-#endif
-#ifndef MCM_HARNESS
-constexpr int g_ln_cluster = 0, g_lnc_spin = -1, g_ln_row = 0;
-#endif
-// The tail's coherence argument needs every workgroup with the same blockIdx & 7 on the same XCD (one L2).  That is
-// how the dispatcher deals workgroups in the default (SPX) mode; it is checked on the device, once per handle, with
-// the grid the persistent kernels use: XCC_ID of every workgroup.  Anything else (another partition mode, a masked
-// lease) and the tail is simply not used.
-__global__ void xcc_probe_kernel(unsigned int* out) {
-  if (threadIdx.x == 0) {
-    unsigned int id;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
-    out[blockIdx.x] = id & 0xfu;
-  }
-}
-bool xcd_round_robin(mcm_handle* h, int grid) {
-  if (grid < 8 || grid % 8 || grid > 1024) return false;
-  unsigned int* dev = nullptr;
-  if (hipMalloc((void**)&dev, (size_t)grid * sizeof(unsigned int)) != hipSuccess) return false;
-  std::vector<unsigned int> ids((size_t)grid, 0xffu);
-  bool ok = true;
-  for (int rep = 0; rep < 3 && ok; ++rep) {  // (the mapping must not depend on what ran before)
-    hipLaunchKernelGGL(xcc_probe_kernel, dim3(grid), dim3(512), 0, 0, dev);
-    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipMemcpy(ids.data(), dev, (size_t)grid * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess;
-    for (int b = 0; ok && b < grid; ++b) ok = ids[(size_t)b] == ids[(size_t)(b & 7)];
-    for (int i = 0; ok && i < 8; ++i)
-      for (int j = 0; ok && j < i; ++j) ok = ids[(size_t)i] != ids[(size_t)j];
-  }
-  (void)hipFree(dev);
-  return ok;
 }
 
 // CLIPEncoderLayer.forward ×layers on x [nseq*L, D] (fp32, in place).
@@ -381,116 +287,37 @@ bool xcd_round_robin(mcm_handle* h, int grid) {
 // consumed rows (every op after attention is row-wise), 1/12 less work for a 12-layer tower.
 // ln1_of_layer0_done: the caller has already produced layer 0's layer_norm1 output in h->ln (the vision tower fuses it
 // with pre_layrnorm, launch_layernorm_pre)
-// fold_ok (vision tower) and the harness switch mcm_debug_ln_fold(1): LayerNorm fold, an A/B arm (measured 1 % slower
-// end to end than the LayerNorm launches; the shipped library never takes it).  The LayerNorm between a
-// residual GEMM and the GEMM behind it is not launched: the residual epilogue also writes z = gamma o x (into h->ln,
-// where the LayerNorm output would have gone) and the row moments, fold_stats turns those into (rstd, mean rstd) per
-// row, and the consumer's epilogue normalises (gemm.hip, "LayerNorm fold").  Not for the layer the caller pools row 0 of
-// (its LayerNorms see other rows / strides) and not for layer 0's layer_norm1 (fused with pre_layrnorm by the caller).
 // x2 (fp16 vision tower; the split-activation arm, mcm_score_x2): every activation that feeds an MFMA — LayerNorm outputs,
 // q / k / v, the attention output, the QuickGELU output — is carried as a split image (hi + lo, twice the columns) and every
 // GEMM runs GemmArgs::xsplit; the residual stream, LayerNorm statistics and softmax are fp32 as always.
+// arms: the A/B builds' per-call plan (mcm_api_arms.hpp), asked at three points of a whole-batch layer; in the shipped
+// library every answer is "no" and the layer below is all there is.
 int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bool causal,
-               bool pooled_row0, bool ln1_of_layer0_done = false, bool fold_ok = false, bool x2 = false) {
+               bool pooled_row0, bool ln1_of_layer0_done = false, bool x2 = false) {
   const int M = nseq * L, D = t.D, P = t.prec;
   const int es = prec_esize(P);
-  const int Mp = (int)padded_rows(h, M);
   const int ks = t.split ? 1 : 0;
   const int xs = x2 ? 1 : 0;
   const int hd = D / t.heads;  // 64, or 80 (mcm_create admits nothing else)
-  // the harness A/B arms (LayerNorm fold / tail / cluster / ROW64, head-major qkv) know head_dim 64 and widths <= 1024 only
-  const bool arms_ok = hd == 64 && D <= 1024;
   const bool erf = t.act == MCM_ACT_GELU;  // the tower's MLP activation: exact GELU (OpenCLIP-trained) or QuickGELU (OpenAI)
   const int epi_store = x2 ? EPI_STORE_X2 : EPI_STORE;
   const int epi_act = erf ? (x2 ? EPI_GELU_ERF_X2 : EPI_GELU_ERF) : (x2 ? EPI_GELU_X2 : EPI_GELU);
-  if (x2 || erf || !arms_ok) fold_ok = false;  // (the LayerNorm fold's consumer epilogue is an A/B arm: QuickGELU only)
   const size_t wrow = (size_t)D * es * (t.split ? 2 : 1);  // bytes per row of a [*, D] weight image
-  // producer form: 1 = fused into the residual GEMM's epilogue (ping-pong kernel), 2 = plain residual GEMM + fold_rows
-  // (tile kernel: small batches) - bit-identical; the consumers need a fold epilogue in whichever kernel they take
-  const int pkind = gemm_fold_kind(EPI_RESID, Mp, D);
-  const bool can_fold = fold_ok && g_ln_fold && g_qkv_chunks == 1 && h->fold_part && P != MCM_PREC_F32 && !t.split &&
-                        t.L[0].cqkv != nullptr && pkind != 0 && gemm_fold_kind(EPI_STORE, Mp, 3 * D) != 0 &&
-                        gemm_fold_kind(EPI_GELU, Mp, t.ff) != 0;
-  auto produce = [&](GemmArgs& g, const float* gamma) -> hipError_t {  // residual GEMM + z / moments / statistics
-    if (pkind == 1) { g.fold_z = h->ln; g.fold_g = gamma; g.fold_part = h->fold_part; }
-    hipError_t e = gemm(h, s, P, EPI_RESID, g);
-    if (e == hipSuccess && pkind == 2) {
-      Scope sc(h, s, MCM_KC_LAYERNORM, 6.0 * Mp * D);
-      e = launch_fold_rows(P, h->x, gamma, h->ln, h->fold_part, Mp, D, s, h->sat_on ? h->sat_dev : nullptr);
-    }
-    return e == hipSuccess ? fold_stats(h, s, Mp, D) : e;
-  };
-  bool ln1_folded = false;  // h->ln holds gamma1 o x and h->fold_rs the row statistics of this layer's layer_norm1
-  // LayerNorm in the tail: the residual GEMMs of whole-batch layers also produce the LayerNorm that follows them
-  const bool tail_ok0 = arms_ok && g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && Mp % 256 == 0 && Mp / 256 <= h->ln_cap8 * 8 &&
-                        gemm_ln_tail_ok(P, Mp, D);
-  // LayerNorm by the row panel's cluster (LNC, harness arm): the same hand-over of gamma / beta / output / counters, plus the
-  // slot-moment buffer; the residual epilogue itself writes the LayerNorm output (no idle-wave tickets, no re-read of x)
-  const bool cluster_ok = arms_ok && g_ln_cluster && !g_ln_tail && !x2 && !can_fold && !t.split && h->ln_state && h->fold_part && Mp % 256 == 0 &&
-                          2 * ((Mp / 256 + 7) / 8) <= h->ln_cap8 && gemm_ln_tail_ok(P, Mp, D);
-  auto with_tail = [&](GemmArgs& g, const float* gamma, const float* beta) {
-    g.ln_g = gamma; g.ln_b = beta; g.ln_y = h->ln; g.ln_eps = h->cfg.ln_eps;
-    g.ln_state = h->ln_state; g.ln_rs = h->ln_rs; g.ln_cap8 = h->ln_cap8;
-    if (cluster_ok) { g.lnc = 1; g.fold_part = h->fold_part; g.lnc_spin = g_lnc_spin; }
-  };
-  // LNC defer form: the clean-up launch behind a residual GEMM that ran with GemmArgs::lnc (a few hundred workgroups that read one
-  // mask word and exit, plus the segments the GEMM's waves did not wait for)
-  auto lnc_cleanup = [&](const float* gamma, const float* beta) -> hipError_t {
-#ifdef MCM_HARNESS
-    if (!cluster_ok || g_lnc_spin < 0) return hipSuccess;
-    Scope sc(h, s, MCM_KC_LAYERNORM, 8.0 * Mp * D);
-    return launch_lnc_cleanup(P, h->x, gamma, beta, h->ln, h->fold_part, Mp, D, h->cfg.ln_eps, h->ln_state, h->ln_rs, h->ln_cap8, s,
-                              h->sat_on ? h->sat_dev : nullptr);
-#else
-    return hipSuccess;
-#endif
-  };
-  // ROW64 arm (harness): the residual GEMM as 64-row full-row tiles whose epilogue writes x and the LayerNorm output
-  const bool row_ok = arms_ok && g_ln_row && !g_ln_tail && !g_ln_cluster && !x2 && !can_fold && !t.split && P != MCM_PREC_F32 && Mp % 64 == 0 &&
-                      (D == 768 || D == 1024) && t.ff % 128 == 0;
-  auto row_gemm = [&](GemmArgs g, const float* gamma, const float* beta, void** blk) -> hipError_t {
-#ifdef MCM_HARNESS
-    g.ln_g = gamma; g.ln_b = beta; g.ln_y = h->ln; g.ln_eps = h->cfg.ln_eps;
-    g.M = Mp; g.sat = h->sat_on ? h->sat_dev : nullptr;
-    if (g_ln_row >= 3) {   // blocked W: built once per weight (not inside a graph capture: the first call allocates)
-      if (!*blk) {
-        if (dev_alloc(h, blk, (size_t)g.N * g.K * 2)) return hipErrorOutOfMemory;
-        hipError_t e = launch_row64_block_w(g.w, *blk, g.N, g.K, s);
-        if (e != hipSuccess) return e;
-      }
-      g.w = *blk;
-      g.wblk = 1;
-    }
-    Scope sc(h, s, MCM_KC_GEMM, 2.0 * g.M * (double)g.N * g.K, g.N == g.K ? MCM_KC_GEMM_OUTPROJ : MCM_KC_GEMM_FC2);
-    return launch_gemm_row64_ln(P, g, s, (g_ln_row == 2 || g_ln_row == 4) ? 3 : 2);
-#else
-    (void)g; (void)gamma; (void)beta; (void)blk;
-    return hipErrorInvalidValue;
-#endif
-  };
-  const bool tail_ok = tail_ok0 || cluster_ok || row_ok;   // any of the arms: the residual GEMM also produces the LayerNorm behind it
-  bool ln1_by_tail = false;  // h->ln already holds this layer's layer_norm1 (written by the previous layer's fc2)
+  Arms arms(h, s, t, nseq, L, pooled_row0, x2);
+  int rc = MCM_OK;
+  bool ln1_done = ln1_of_layer0_done;  // h->ln already holds this layer's layer_norm1
   for (int l = 0; l < t.layers; ++l) {
     const LayerW& w = t.L[l];
     const bool cls = pooled_row0 && l == t.layers - 1 && L > 1;
-    if (!(l == 0 && ln1_of_layer0_done) && !ln1_folded && !ln1_by_tail)
-      HIP_TRY(h, lnorm(h, s, P, h->x, w.ln1w, w.ln1b, h->ln, M, D, false, x2));
-    ln1_by_tail = false;
+    if (!ln1_done) HIP_TRY(h, lnorm(h, s, P, h->x, w.ln1w, w.ln1b, h->ln, M, D, false, x2));
     if (!cls) {
-      const int nch = (!x2 && g_qkv_chunks > 1 && nseq % g_qkv_chunks == 0) ? g_qkv_chunks : 1;
-      for (int c = 0; c < nch; ++c) {
-        const int sq = nseq / nch, r0 = c * sq * L;
-        GemmArgs a{};
-        a.x = (const char*)h->ln + (size_t)r0 * D * es; a.w = w.wqkv; a.bias = w.bqkv;
-        a.out = (char*)h->qkv + (size_t)r0 * 3 * D * es;
-        a.M = sq * L; a.N = 3 * D; a.K = D; a.ldx = D; a.ldo = 3 * D; a.ksplit = ks; a.xsplit = xs;
-        if (ln1_folded) { a.bias = w.bqkvf; a.fold_rs = h->fold_rs; a.fold_c = w.cqkv; }
-        // whole-batch launches of a 16-bit tower hand q / k / v over head-major (same bytes in h->qkv, other order;
-        // the row-0-only layer below and the fp32 towers keep [rows][3 D])
-        const int hm = (g_qkv_head_major && !x2 && nch == 1 && P != MCM_PREC_F32 && t.heads * 64 == D) ? Mp : 0;
-        a.hm = hm;
+      GemmArgs a{};
+      a.x = h->ln; a.w = w.wqkv; a.bias = w.bqkv; a.out = h->qkv;
+      a.M = M; a.N = 3 * D; a.K = D; a.ldx = D; a.ldo = 3 * D; a.ksplit = ks; a.xsplit = xs;
+      arms.consumer(a, l, false);
+      if (!arms.qkv_attention(a, epi_store, causal, rc)) {
         HIP_TRY(h, gemm(h, s, P, epi_store, a));
-        HIP_TRY(h, attn(h, s, P, sq, L, t.heads, hd, causal, 0, c * sq, hm, x2));
+        HIP_TRY(h, attn(h, s, P, nseq, L, t.heads, hd, causal, 0, 0, 0, x2));
       }
     } else {
       GemmArgs kv{};  // K and V of every token: weight rows [D, 3D), output columns [D, 3D)
@@ -504,50 +331,30 @@ int run_layers(mcm_handle* h, hipStream_t s, const Tower& t, int nseq, int L, bo
       HIP_TRY(h, gemm(h, s, P, epi_store, q));
       HIP_TRY(h, attn(h, s, P, nseq, L, t.heads, hd, causal, 1, 0, 0, x2));
     }
+    if (rc) return rc;
     const int Mr = cls ? nseq : M;            // rows that continue
     const int rs = cls ? L * D : D;           // their stride in x / att
-    const bool fold2 = can_fold && !cls;      // layer_norm2 folded into out-proj / fc1
     GemmArgs o{};
     o.x = h->att; o.w = w.wo; o.bias = w.bo; o.resid = h->x;
     o.M = Mr; o.N = D; o.K = D; o.ldx = rs; o.ldo = rs; o.ksplit = ks; o.xsplit = xs;
-    if (fold2) {
-      HIP_TRY(h, produce(o, w.ln2w));
-    } else if (row_ok && !cls) {
-      HIP_TRY(h, row_gemm(o, w.ln2w, w.ln2b, const_cast<void**>(&t.L[l].wo_blk)));
-    } else if (tail_ok && !cls) {
-      with_tail(o, w.ln2w, w.ln2b);  // layer_norm2 by the out-proj kernel's idle waves
-      HIP_TRY(h, gemm(h, s, P, EPI_RESID, o));
-      HIP_TRY(h, lnc_cleanup(w.ln2w, w.ln2b));
-    } else {
+    if (cls || !arms.resid_ln(o, l, false, w.ln2w, w.ln2b, rc)) {  // out-proj, then layer_norm2
       HIP_TRY(h, gemm(h, s, P, EPI_RESID, o));
       if (!cls) HIP_TRY(h, lnorm(h, s, P, h->x, w.ln2w, w.ln2b, h->ln, M, D, false, x2));
       else HIP_TRY(h, lnorm_strided(h, s, P, h->x, w.ln2w, w.ln2b, h->ln, Mr, D, (size_t)rs, (size_t)D * (1 + xs), x2));
     }
+    if (rc) return rc;
     GemmArgs f1{};
     f1.x = h->ln; f1.w = w.w1; f1.bias = w.b1; f1.out = h->hbuf;
     f1.M = Mr; f1.N = t.ff; f1.K = D; f1.ldx = D; f1.ldo = t.ff; f1.ksplit = ks; f1.xsplit = xs;
-    if (fold2) { f1.bias = w.b1f; f1.fold_rs = h->fold_rs; f1.fold_c = w.c1; }
+    arms.consumer(f1, l, true);
     HIP_TRY(h, gemm(h, s, P, epi_act, f1));
-    // the next layer's layer_norm1 folded into fc2 / the next QKV projection (not into the row-0-only layer)
-    ln1_folded = fold2 && l + 1 < t.layers && !(pooled_row0 && l + 1 == t.layers - 1 && L > 1);
     GemmArgs f2{};
     f2.x = h->hbuf; f2.w = w.w2; f2.bias = w.b2; f2.resid = h->x;
     f2.M = Mr; f2.N = D; f2.K = t.ff; f2.ldx = t.ff; f2.ldo = rs; f2.ksplit = ks; f2.xsplit = xs;
-    if (ln1_folded) {
-      HIP_TRY(h, produce(f2, t.L[l + 1].ln1w));
-    } else {
-      if (row_ok && !cls && l + 1 < t.layers) {
-        ln1_by_tail = true;
-        HIP_TRY(h, row_gemm(f2, t.L[l + 1].ln1w, t.L[l + 1].ln1b, const_cast<void**>(&t.L[l].w2_blk)));
-      } else {
-        if (tail_ok && !cls && l + 1 < t.layers) {  // the next layer's layer_norm1 (all rows, also in front of a row-0-only layer)
-          with_tail(f2, t.L[l + 1].ln1w, t.L[l + 1].ln1b);
-          ln1_by_tail = true;
-        }
-        HIP_TRY(h, gemm(h, s, P, EPI_RESID, f2));
-        if (ln1_by_tail) HIP_TRY(h, lnc_cleanup(t.L[l + 1].ln1w, t.L[l + 1].ln1b));
-      }
-    }
+    // fc2; the next layer's layer_norm1 is that layer's first launch unless an arm produces it here
+    ln1_done = !cls && l + 1 < t.layers && arms.resid_ln(f2, l, true, t.L[l + 1].ln1w, t.L[l + 1].ln1b, rc);
+    if (!ln1_done) HIP_TRY(h, gemm(h, s, P, EPI_RESID, f2));
+    if (rc) return rc;
   }
   return MCM_OK;
 }
@@ -578,16 +385,7 @@ int build_tower(mcm_handle* h, Tower& t, const std::string& tower, hipStream_t s
     HIP_TRY(h, cvt(W(h, pre + ".self_attn.out_proj.weight"), w.wo, D, D));
     HIP_TRY(h, cvt(W(h, pre + ".mlp.fc1.weight"), w.w1, ff, D));
     HIP_TRY(h, cvt(W(h, pre + ".mlp.fc2.weight"), w.w2, D, ff));
-    if (&t == &h->vis && h->fold_part && !t.split) {  // LayerNorm fold: the column vectors of the two LayerNorm consumers
-      if ((rc = dev_alloc(h, (void**)&w.cqkv, (size_t)3 * D * sizeof(float)))) return rc;
-      if ((rc = dev_alloc(h, (void**)&w.bqkvf, (size_t)3 * D * sizeof(float)))) return rc;
-      if ((rc = dev_alloc(h, (void**)&w.c1, (size_t)ff * sizeof(float)))) return rc;
-      if ((rc = dev_alloc(h, (void**)&w.b1f, (size_t)ff * sizeof(float)))) return rc;
-      HIP_TRY(h, launch_fold_prep(prec, w.wqkv, W(h, pre + ".layer_norm1.weight"), W(h, pre + ".layer_norm1.bias"),
-                                  w.bqkv, w.cqkv, w.bqkvf, 3 * D, D, s));
-      HIP_TRY(h, launch_fold_prep(prec, w.w1, W(h, pre + ".layer_norm2.weight"), W(h, pre + ".layer_norm2.bias"),
-                                  W(h, pre + ".mlp.fc1.bias"), w.c1, w.b1f, ff, D, s));
-    }
+    if ((rc = Arms::build_layer(h, t, l, pre, s))) return rc;
     w.bo = W(h, pre + ".self_attn.out_proj.bias");
     w.b1 = W(h, pre + ".mlp.fc1.bias");
     w.b2 = W(h, pre + ".mlp.fc2.bias");
@@ -727,23 +525,7 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
   if (!rc && hipHostMalloc((void**)&h->rowidx_pin, (size_t)mt * sizeof(int32_t)) != hipSuccess)
     rc = fail(h, MCM_ENOMEM, "hipHostMalloc rowidx");
   if (!rc) rc = dev_alloc(h, (void**)&h->prep_dev, (size_t)mcm_handle::PREP_RING * c.max_batch * sizeof(PrepImage));
-#if defined(MCM_HARNESS) || defined(MCM_LN_FOLD)  // LayerNorm fold (A/B arm): row moments and row statistics
-  if (!rc && c.precision != MCM_PREC_F32 && c.v_width % 256 == 0 && c.v_mlp % 256 == 0 && c.v_width <= 1024 &&
-      c.v_width == c.v_heads * 64) {   // (the arm knows head_dim 64 and widths <= 1024: run_layers arms_ok)
-    rc = dev_alloc(h, (void**)&h->fold_part, (size_t)(c.v_width / 64) * mv * sizeof(float2));
-    if (!rc) rc = dev_alloc(h, (void**)&h->fold_rs, (size_t)mv * sizeof(float2));
-  }
-#endif
-#if defined(MCM_HARNESS) || defined(MCM_LN_TAIL)  // LayerNorm in the tail (A/B arm): its counters, if the device qualifies
-  if (!rc && c.precision != MCM_PREC_F32 && (c.v_width == 768 || c.v_width == 1024) && xcd_round_robin(h, gemm_persistent_grid())) {
-    h->ln_cap8 = 2 * (int)((mv / 256 + 7) / 8);  // (x 2: the cluster arm counts the upper and lower half of a row panel separately)
-    h->ln_rs = (2 * h->ln_cap8 + 4 + 63) / 64 * 64;  // words per XCD region: whole 256-B blocks, no line shared between XCDs
-                                                     // ([cap8] counters, 3 words, [cap8] segment masks + 1 word of the LNC defer form)
-    const size_t bytes = (size_t)8 * h->ln_rs * sizeof(unsigned int);
-    rc = dev_alloc(h, (void**)&h->ln_state, bytes);
-    if (!rc && hipMemset(h->ln_state, 0, bytes) != hipSuccess) rc = fail(h, MCM_EHIP, "hipMemset LayerNorm-tail state");
-  }
-#endif
+  if (!rc) rc = Arms::create(h, mv);
   if (!rc) rc = dev_alloc(h, (void**)&h->sat_dev, 16);
   if (!rc && hipMemset(h->sat_dev, 0, 16) != hipSuccess) rc = fail(h, MCM_EHIP, "hipMemset saturation counter");
   if (!rc && hipHostMalloc((void**)&h->fault_pin, 64, hipHostMallocMapped) != hipSuccess) rc = fail(h, MCM_ENOMEM, "hipHostMalloc fault word");
@@ -973,7 +755,7 @@ int encode_image_impl(mcm_handle* h, const void* pixels_dev, bool u8, int32_t B,
   const mcm_config& c = h->cfg;
   const int D = c.v_width;
   if ((rc = vision_front(h, s, pixels_dev, u8, B, x2))) return rc;
-  if ((rc = run_layers(h, s, h->vis, B, h->ntok, false, true, true, true, x2))) return rc;
+  if ((rc = run_layers(h, s, h->vis, B, h->ntok, false, true, true, x2))) return rc;
   {
     Scope sc(h, s, MCM_KC_POOL_PROJECT, 2.0 * B * D * c.proj_dim);
     HIP_TRY(h, launch_pool_project(h->x, nullptr, h->ntok, B, D,

@@ -1,4 +1,4 @@
-"""LayerNorm fold (gemm.hip / mcm_api.hip run_layers), an A/B arm of the harness library (mcm_debug_ln_fold; measured 1 %
+"""LayerNorm fold (gemm.hip / mcm_api_arms.hpp Arms), an A/B arm of the harness library (mcm_debug_ln_fold; measured 1 %
 slower end to end than the LayerNorm launches, so the shipped library does not take it): in the 16-bit modes the
 LayerNorms of the vision tower between a residual GEMM and the GEMM that consumes their output are not launched — the
 residual epilogue writes gamma o x and the row moments, the consumer's epilogue normalises.  Checked here:

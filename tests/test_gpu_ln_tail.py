@@ -1,4 +1,4 @@
-"""LayerNorm in the tail of the residual GEMMs (gemm.hip "LayerNorm in the tail"; mcm_api.hip run_layers): the LayerNorm
+"""LayerNorm in the tail of the residual GEMMs (gemm.hip "LayerNorm in the tail"; mcm_api_arms.hpp Arms): the LayerNorm
 behind a whole-batch out-proj / fc2 of a 16-bit vision tower is computed by that GEMM's own waves once they have run
 out of tiles — same arithmetic as the LayerNorm kernel (ln_row.hpp), so scores must be bit-identical to the run with
 every LayerNorm launched (harness switch mcm_debug_ln_tail), for every launch of a long series (the tail is driven by
