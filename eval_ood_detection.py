@@ -1,6 +1,6 @@
 """eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
 and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`).
+`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`).
 
 Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
 set) → AUROC / AUPR / FPR95 → log + CSV.
@@ -54,7 +54,7 @@ def process_args(argv=None):
                             "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
-                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha"], help="score options")
+                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn"], help="score options")
     # Mahalanobis baseline (--score maha), reference eval_ood_detection.py:38-44
     p.add_argument("--feat_dim", type=int, default=512)
     p.add_argument("--normalize", type=bool, default=False)
@@ -109,19 +109,29 @@ def process_args(argv=None):
                         "set's idx / prob / scores / labels to predictions_<set>.npz in the log directory (rank 0 under torchrun).  "
                         "Threshold refinement keeps working and patches the SCORES only: predictions are those of the arm that "
                         "scored the image first, so for the few hundred re-scored images prob[:,0] and -score differ in their last "
-                        "bits.  Not available with --score maha")
+                        "bits.  Not available with --score maha / knn")
     p.add_argument("--maha-fit", default="host", choices=["host", "device"],
                    help="how --score maha fits its statistics: host (the reference's recipe: every training feature copied to the "
                         "host, torch.cov in float64 there, on rank 0 only under torchrun) or device (running fp64 sums in HBM, one "
                         "kernel per batch, every rank fitting its own shard of the training set and one all-reduce at the end; "
                         "same class means bit for bit, the covariance within its fp64 error budget)")
+    p.add_argument("--knn-k", default=0, type=int, metavar="K",
+                   help="--score knn (deep k-nearest neighbours, Sun et al. 2022: the distance from an image's unit-norm feature "
+                        "to its K-th nearest neighbour among the training features, no prompt bank): K, 1..1024 and at most the "
+                        "bank's rows; 0 (default) = min(1024, max(1, round(bank rows / 1281))), their k = 1000 at ImageNet-1k "
+                        "scaled linearly.  The bank is the \"train\" set (--subset / --max_count as for --score maha), encoded by "
+                        "every rank's shard and all-gathered")
     args = p.parse_args(argv)
+    if not 0 <= args.knn_k <= 1024:
+        p.error("--knn-k K: K must be 1..1024 (0 = chosen from the bank size)")
+    if args.score == "knn" and args.refine_threshold in ("on", "exact"):
+        p.error("--refine-threshold on needs a 16-bit --dtype and an MCM-family --score")
     if args.maha_fit == "device" and args.score != "maha":
         p.error("--maha-fit device needs --score maha (no other score fits anything)")
     if args.predict:
-        if args.score == "maha":
-            p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the Mahalanobis "
-                    "baseline (--score maha) has no prompt bank to match against")
+        if args.score in ("maha", "knn"):
+            p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the training-set "
+                    "baselines (--score maha, --score knn) have no prompt bank to match against")
         if not 1 <= args.predict <= 8:
             p.error("--predict K: K must be 1..8")
     if args.decoder:
@@ -257,7 +267,8 @@ def main(argv=None):
     # the split-activation workspace of an fp16 handle (include/mcm.h mcm_config.x2_max_batch): the whole run goes
     # through that arm with --dtype fp16x2 (full batch: twice the activation bytes); threshold refinement re-scores a few hundred
     # images, for which half the batch costs nothing extra; otherwise the workspace is not allocated at all
-    will_refine = args.refine_threshold != "off" and args.score != "maha"
+    no_bank = args.score in ("maha", "knn")   # the training-set baselines: no prompt bank, scores come back as host arrays
+    will_refine = args.refine_threshold != "off" and not no_bank
     x2_batch = 0 if args.dtype == "fp16x2" else (max(1, args.batch_size // 2) if (args.dtype == "fp16" and will_refine) else -1)
     net = build_model(args.CLIP_ckpt, weights=args.weights, device=dev, precision=args.dtype,
                       max_batch=args.batch_size, synthetic_regime=args.synthetic_weights,
@@ -282,7 +293,7 @@ def main(argv=None):
     sources = {}
     test_loader = _loader(args, net, "id", N_ID[args.in_dataset], False, sources)
     test_labels = get_test_labels(args, test_loader)
-    on_dev = not args.host_metrics and args.score != "maha"  # scores stay in HBM; three metrics come back
+    on_dev = not args.host_metrics and not no_bank  # scores stay in HBM; three metrics come back
     if args.score == "maha":  # reference eval_ood_detection.py:72-79
         args.feat_dim = net.geo.proj_dim
         os.makedirs(args.template_dir, exist_ok=True)
@@ -321,12 +332,24 @@ def main(argv=None):
             mdist.broadcast_tensors([stats["classwise_mean"], stats["precision"]], src=0)
         classwise_mean, precision = stats["classwise_mean"], stats["precision"]
         in_score = get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_dist=True)
+    elif args.score == "knn":
+        from mcm_amd.detection import get_knn_bank, get_knn_score, knn_auto_k
+
+        # every rank encodes its shard of the training set; the bank is all-gathered and stays in HBM for the run
+        n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
+        knn_bank = get_knn_bank(args, net, _loader(args, net, "train", n_train, False, sources))
+        knn_k = args.knn_k or knn_auto_k(len(knn_bank))
+        if knn_k > len(knn_bank):
+            raise SystemExit(f"--knn-k {knn_k} exceeds the bank's {len(knn_bank)} rows")
+        log.debug(f"--score knn: k = {knn_k}{'' if args.knn_k else ' (auto)'}, bank of {len(knn_bank)} unit-norm training features "
+                  f"x {knn_bank.shape[1]} ({sources['train']['kind']})")
+        in_score = get_knn_score(args, net, test_loader, knn_bank, knn_k)
     else:
         in_score = _score_set(args, net, test_loader, test_labels, "id", log, rank, on_dev, in_dist=True)
         _note_pillow_files(net, sources, "id", log)
     net.warn_if_saturated(f"the ID set {args.in_dataset}")
     refiner, net32 = None, None
-    refinable = args.score != "maha" and args.dtype in ("fp16", "bf16")  # (fp16x2 / fp32 runs ARE exact-grade arms; with
+    refinable = not no_bank and args.dtype in ("fp16", "bf16")  # (fp16x2 / fp32 runs ARE exact-grade arms; with
                                                                        # --host-metrics the scores are host arrays: refined in place too)
     if args.refine_threshold != "off" and refinable:
         from mcm_amd.detection import prompt_bank
@@ -362,6 +385,8 @@ def main(argv=None):
         log.debug(f"data source: {sources[out_dataset]}")
         if args.score == "maha":
             out_score = get_Mahalanobis_score(args, net, ood_loader, classwise_mean, precision, in_dist=False)
+        elif args.score == "knn":
+            out_score = get_knn_score(args, net, ood_loader, knn_bank, knn_k)
         else:
             out_score = _score_set(args, net, ood_loader, test_labels, out_dataset, log, rank, on_dev)
             _note_pillow_files(net, sources, out_dataset, log)

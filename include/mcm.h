@@ -41,7 +41,8 @@ extern "C" {
                           * MCM_LINEAR_ACT_GELU flag of mcm_op_linear_ex
                           * (still 5) mcm_score_features_topk / mcm_score_topk: two added symbols, no struct, constant or
                           * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged
-                          * (still 5) mcm_maha_fit_accumulate: an added symbol, on the same terms */
+                          * (still 5) mcm_maha_fit_accumulate: an added symbol, on the same terms
+                          * (still 5) mcm_knn_workspace_bytes / mcm_knn_score_features: two added symbols, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -367,6 +368,37 @@ int mcm_maha_score_features(mcm_handle* h, const float* feats_dev, int32_t B, co
 int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
                             const float* shift_dev /* [proj_dim] or NULL */, double* gram_dev, double* sum_dev,
                             void* stream);
+
+/* ---- deep k-nearest-neighbour baseline (--score knn; Sun et al. 2022) --------------------------------
+ * The other training-set baseline: the distance from a feature row to its k-th nearest neighbour among the rows of a
+ * bank of training features (added under ABI 5: two symbols only).  P = the handle's proj_dim, everything row-major:
+ *   s[b, n]     = the fp32 dot product of feats_dev[b] and bank_dev[n]: every product rounded once into one fp32
+ *                 accumulator chain over the P columns (the exact-fp32 MFMA), operands never narrowed;
+ *   topv[b, :]  = the k largest s[b, .] as a multiset, sorted descending.  A NaN similarity is never selected, -0 and
+ *                 +0 compare equal (and are both written as +0), slots with no candidate left (k > N, NaNs) hold -inf;
+ *   scores[b]   = (float) sqrt(max(0, 2 - 2 (double) topv[b, k - 1])): for unit-norm rows the Euclidean distance to
+ *                 the k-th nearest neighbour; larger = more OOD, the sign every stored score here has; -inf gives +inf.
+ * The [B, N] similarities exist in registers and LDS only.  The bank is cut into `splits` contiguous ranges of
+ * ceil(N / splits) rows (the last ones may be short or empty); each keeps a k-entry list per query in work_dev
+ * (splits * B * k floats), a second launch merges them.  splits = 0: the library chooses from B, N and the device's CU
+ * count; n > 0: exactly n, at most MCM_KNN_MAX_SPLITS.  A tuning argument only: the outputs are a pure function of
+ * feats_dev, bank_dev and k — the same bits for every `splits`, for every cut of the queries into calls and on every
+ * run (no atomics, nothing summed across workgroups, no workgroup waits for another).
+ * mcm_knn_workspace_bytes: *bytes_out = the work_dev size mcm_knn_score_features needs for the same (B, N, k, splits);
+ * with splits = 0 it resolves the split count on the CURRENT device, as the score call does.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, graph-capturable (after one call outside the
+ * capture, which sets the kernels' LDS attribute); timed under MCM_KC_SCORE (2 B N P flop).
+ * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
+ * B < 1, N < 1, k outside 1 .. MCM_KNN_MAX_K, splits < 0 or > MCM_KNN_MAX_SPLITS, work_bytes below
+ * mcm_knn_workspace_bytes, proj_dim % 4 != 0, or feats_dev / bank_dev not 16-byte aligned (rows are read 16 bytes at a
+ * time).  topv_dev may be NULL. */
+#define MCM_KNN_MAX_K 1024
+#define MCM_KNN_MAX_SPLITS 32
+int mcm_knn_workspace_bytes(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int64_t* bytes_out);
+int mcm_knn_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
+                           const float* bank_dev /* [N, proj_dim] */, int64_t N, int32_t k, int32_t splits,
+                           void* work_dev, int64_t work_bytes, float* scores_dev /* [B] */,
+                           float* topv_dev /* [B, k] or NULL */, void* stream);
 
 /* ---- CLIP byte-level BPE tokenizer, host side --------------------------------
  * Replaces CLIPTokenizer.from_pretrained(args.ckpt) + tokenizer(list[str], padding=True,

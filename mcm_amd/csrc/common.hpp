@@ -423,6 +423,13 @@ hipError_t launch_maha_score(const float* feats, int B, const float* prec, const
 hipError_t launch_maha_fit(const float* feats, int B, int P, const float* shift, double* gram, double* sum,
                            hipStream_t s);
 
+// knn.hip: the k largest fp32 similarities of every feats row against bank [N, P], sorted descending, into topv [B, k]
+// (or nullptr), and scores [B] = sqrt(max(0, 2 - 2 topv[:, k - 1])); work holds S * B * k floats (the partial lists of
+// the S bank splits).  knn_auto_splits: the S the library picks from N, B and the current device's CU count.
+int knn_auto_splits(int B, int64_t N);
+hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, int P, int k, int S, float* work,
+                      float* scores, float* topv, hipStream_t s);
+
 hipError_t launch_score(const float* img, int B, const float* text, int K, int P, float T,
                         int kind, float* scores, hipStream_t s);
 // the top-k form of the same tail (score_kernel<true>): idx [B,topk] int32, prob [B,topk] fp32 or nullptr;

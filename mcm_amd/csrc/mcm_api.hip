@@ -833,6 +833,39 @@ int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev, int32_t B, co
   return MCM_OK;
 }
 
+namespace {
+// the argument rules both k-NN entries share; *S_out = the split count the call runs with
+int knn_check(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int* S_out) {
+  if (B < 1 || N < 1 || k < 1 || k > MCM_KNN_MAX_K || splits < 0 || splits > MCM_KNN_MAX_SPLITS) return MCM_EINVAL;
+  if (h->cfg.proj_dim < 4 || h->cfg.proj_dim % 4) return MCM_EINVAL;
+  *S_out = splits ? splits : knn_auto_splits(B, N);
+  return MCM_OK;
+}
+}  // namespace
+
+int mcm_knn_workspace_bytes(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int64_t* bytes_out) {
+  int S = 0;
+  if (!h || !bytes_out || knn_check(h, B, N, k, splits, &S)) return MCM_EINVAL;
+  *bytes_out = (int64_t)S * B * k * (int64_t)sizeof(float);
+  return MCM_OK;
+}
+
+int mcm_knn_score_features(mcm_handle* h, const float* feats_dev, int32_t B, const float* bank_dev, int64_t N, int32_t k,
+                           int32_t splits, void* work_dev, int64_t work_bytes, float* scores_dev, float* topv_dev,
+                           void* stream) {
+  if (!h) return MCM_EINVAL;
+  int S = 0;
+  if (!feats_dev || !bank_dev || !work_dev || !scores_dev || knn_check(h, B, N, k, splits, &S))
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (((uintptr_t)feats_dev | (uintptr_t)bank_dev) & 15) return fail(h, MCM_EINVAL, "feats_dev / bank_dev must be 16-byte aligned");
+  if (work_bytes < (int64_t)S * B * k * (int64_t)sizeof(float))
+    return fail(h, MCM_EINVAL, "work_bytes is below mcm_knn_workspace_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * (double)N * h->cfg.proj_dim);
+  HIP_TRY(h, launch_knn(feats_dev, B, bank_dev, N, h->cfg.proj_dim, k, S, (float*)work_dev, scores_dev, topv_dev, s));
+  return MCM_OK;
+}
+
 int mcm_encode_image_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, float* out_dev,
                         void* stream) {
   return encode_image_impl(h, pixels_dev, true, B, out_dev, stream);

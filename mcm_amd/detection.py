@@ -450,6 +450,84 @@ def get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_
     return res.cpu().numpy().astype(np.float32)
 
 
+def knn_auto_k(n_bank):
+    """The k of `--score knn` for a bank of n_bank rows: Sun et al.'s k = 1000 at ImageNet-1k's 1 281 167 training images
+    (k = 10 at their 1 % subset), scaled linearly and kept inside what `knn_scores` takes: min(1024, max(1, round(n / 1281)))."""
+    return min(1024, max(1, int(round(int(n_bank) / 1281))))
+
+
+def _unit_image_features(net, images):
+    """`get_image_features` then `f / f.norm()` in torch: the k-NN score is defined on unit rows, whatever args.normalize says."""
+    f = net.get_image_features(pixel_values=images).float()
+    return f / f.norm(dim=-1, keepdim=True)
+
+
+def get_knn_bank(args, net, train_loader):
+    """`--score knn`: the bank of unit-norm training features, [n_train, P] fp32 on the net's device, in dataset order, on
+    every rank.  Under world_size > 1 every rank encodes its `shard_range` of the training set (a loader that cannot be
+    sharded by index is refused, as by `get_Mahalanobis_score`) and the shards are all-gathered: the bank is replicated like
+    the prompt bank, images are sharded like everywhere else.  A feature does not depend on the batch it was computed in, so
+    the bank holds the same bits at every world size."""
+    import torch
+
+    if not hasattr(net, "knn_scores"):
+        raise TypeError("get_knn_bank needs a net with knn_scores (a NativeCLIP); there is no eager fallback")
+    rank, ws = mdist.world()
+    n_total = len(train_loader.dataset)
+    batches, lo, hi = train_loader, 0, n_total
+    if ws > 1:
+        lo, hi = mdist.shard_range(n_total, rank, ws)
+        batches = shard_loader(train_loader, lo, hi)
+        if batches is None:
+            raise TypeError("--score knn under world_size > 1 needs a loader that can be sharded by index")
+    parts, seen = [], 0
+    with torch.no_grad():
+        for images, _labels in (batches if hi > lo else ()):
+            if seen >= hi - lo:
+                break
+            f = _unit_image_features(net, images[: hi - lo - seen])
+            parts.append(f)
+            seen += f.shape[0]
+        P = getattr(getattr(net, "geo", None), "proj_dim", None) or getattr(args, "feat_dim", 0)
+        dev = getattr(net, "device", None) or "cpu"
+        local = torch.cat(parts) if parts else torch.empty((0, int(P)), dtype=torch.float32, device=dev)
+        if mdist.group_active():
+            local = mdist.all_gather_rows(local, n_total)
+    return local.detach()[:n_total].contiguous()
+
+
+def get_knn_score(args, net, loader, bank, k):
+    """`--score knn`: per sample sqrt(2 - 2 v_k), v_k the k-th largest dot product of its unit-norm feature with the rows
+    of `bank` (`get_knn_bank`) — the distance to the k-th nearest training feature; larger = more OOD.  Sharded and gathered
+    like `get_ood_scores_clip`; EVERY sample is scored (the drop-the-last-batch rule belongs to the reference's Mahalanobis
+    function only).  Returns a float32 ndarray [len(loader.dataset)]."""
+    import torch
+
+    k = int(k)
+    if not 1 <= k <= len(bank):
+        raise ValueError(f"--score knn: k = {k} needs 1 <= k <= the bank's {len(bank)} rows")
+    rank, ws = mdist.world()
+    n_total = len(loader.dataset)
+    batches, lo, hi = loader, 0, n_total
+    if ws > 1:
+        lo, hi = mdist.shard_range(n_total, rank, ws)
+        batches = shard_loader(loader, lo, hi)
+        if batches is None:
+            raise TypeError("--score knn under world_size > 1 needs a loader that can be sharded by index")
+    out, seen = [], 0
+    with torch.no_grad():
+        for images, _labels in (batches if hi > lo else ()):
+            if seen >= hi - lo:
+                break
+            f = _unit_image_features(net, images[: hi - lo - seen])
+            out.append(net.knn_scores(f, bank, k))
+            seen += f.shape[0]
+    res = torch.cat(out) if out else torch.empty(0, dtype=torch.float32, device=bank.device)
+    if mdist.group_active():
+        res = mdist.all_gather_scores(res, n_total)
+    return res.detach().cpu().numpy().astype(np.float32)[:n_total]
+
+
 def _gather_batch_shards(local, n_total, ws):
     """All-gather score shards whose sizes only the owning rank knows (batch-range split of a generic
     loader: the last batch may be short, batch sizes need not be uniform).  Counts are exchanged first;

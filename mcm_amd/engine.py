@@ -146,6 +146,8 @@ def load_library(harness: bool = False):
     L.mcm_maha_prepare.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.mcm_maha_score_features.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
     L.mcm_maha_fit_accumulate.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.mcm_knn_workspace_bytes.argtypes = [vp, i32, ctypes.c_int64, i32, i32, ctypes.POINTER(ctypes.c_int64)]
+    L.mcm_knn_score_features.argtypes = [vp, vp, i32, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
     L.mcm_measures.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, ctypes.c_double,
                                ctypes.POINTER(ctypes.c_double), vp]
     L.mcm_saturation_check.argtypes = [vp, i32]
@@ -172,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "mcm_kernel_faults",
     "mcm_score_features_topk", "mcm_score_topk",
     "mcm_maha_fit_accumulate",
+    "mcm_knn_workspace_bytes", "mcm_knn_score_features",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -354,6 +357,40 @@ class NativeCLIP:
                                                       state["gram"].data_ptr(), state["sum"].data_ptr(), _stream_ptr()))
         state["n"] += int(f.shape[0])
         return state
+
+    def knn_scores(self, features, bank, k, splits: int = 0, return_values: bool = False):
+        """features [B,P], bank [N,P] fp32 (device) → [B] fp32: sqrt(max(0, 2 - 2 v_k)), v_k the k-th largest fp32 dot
+        product of the row with the bank's rows — for unit-norm rows the distance to the k-th nearest neighbour (include/mcm.h
+        mcm_knn_score_features).  `splits`: 0 = the library's choice, n = the bank in exactly n ranges (a tuning argument: the
+        result does not depend on it).  `return_values=True`: (scores, topv [B,k]), the k largest similarities, descending,
+        -inf where the bank has no candidate left.  The workspace is a buffer of this object that grows on demand; queries
+        go through in blocks of at most 4096 rows."""
+        import torch
+
+        f = features.to(device=self.device, dtype=torch.float32).contiguous()
+        bk = bank.to(device=self.device, dtype=torch.float32).contiguous()
+        P, k, splits = self.geo.proj_dim, int(k), int(splits)
+        if f.dim() != 2 or f.shape[1] != P or bk.dim() != 2 or bk.shape[1] != P:
+            raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
+        B, N = int(f.shape[0]), int(bk.shape[0])
+        scores = torch.empty(B, device=self.device, dtype=torch.float32)
+        topv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32) if return_values else None
+        for s in range(0, max(B, 1), 4096):
+            n = min(4096, B - s)
+            need = ctypes.c_int64(0)
+            self._check_knn(self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, ctypes.byref(need)), n, N, k, splits)
+            work = getattr(self, "_knn_work", None)
+            if work is None or work.numel() * 4 < need.value:
+                work = self._knn_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+            self._check(self._lib.mcm_knn_score_features(
+                self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), N, k, splits, work.data_ptr(), work.numel() * 4,
+                scores[s:s + n].data_ptr(), topv[s:s + n].data_ptr() if return_values else None, _stream_ptr()))
+        return (scores, topv) if return_values else scores
+
+    def _check_knn(self, rc, B, N, k, splits):
+        if rc:
+            raise ValueError(f"knn_scores: refused (rc={rc}) for B={B}, N={N}, k={k}, splits={splits}: B >= 1, N >= 1, "
+                             "1 <= k <= 1024, 0 <= splits <= 32 and proj_dim % 4 == 0 are required")
 
     def get_text_features(self, input_ids, attention_mask=None, normalize: bool = False):
         """[K,S] ids → [K,P] fp32: HF `get_text_features` (the text projection output; unit-norm rows
