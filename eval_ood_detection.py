@@ -1,6 +1,6 @@
 """eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
 and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`).
+`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`, `--neg-*`).
 
 Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
 set) → AUROC / AUPR / FPR95 → log + CSV.
@@ -54,7 +54,7 @@ def process_args(argv=None):
                             "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
-                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn"], help="score options")
+                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel"], help="score options")
     # Mahalanobis baseline (--score maha), reference eval_ood_detection.py:38-44
     p.add_argument("--feat_dim", type=int, default=512)
     p.add_argument("--normalize", type=bool, default=False)
@@ -121,10 +121,32 @@ def process_args(argv=None):
                         "bank's rows; 0 (default) = min(1024, max(1, round(bank rows / 1281))), their k = 1000 at ImageNet-1k "
                         "scaled linearly.  The bank is the \"train\" set (--subset / --max_count as for --score maha), encoded by "
                         "every rank's shard and all-gathered")
+    p.add_argument("--neg-words", default=None, metavar="FILE",
+                   help="--score neglabel (NegLabel, Jiang et al. 2024: the share of an image's softmax mass on the ID prompts of a "
+                        "bank extended by mined negative labels, against every group of negatives alone, averaged): the candidate "
+                        "words, one per line (required with this score; empty lines, duplicates and ID class names are dropped)")
+    p.add_argument("--neg-count", default=0, type=int, metavar="M", help="--score neglabel: keep the M candidates farthest from "
+                   "the ID labels (0 = --neg-frac decides)")
+    p.add_argument("--neg-frac", default=0.15, type=float, help="--score neglabel: keep round(FRAC x candidates) words")
+    p.add_argument("--neg-quantile", default=0.95, type=float, metavar="Q",
+                   help="--score neglabel: a candidate's distance from the ID labels is the Q quantile (linear interpolation) of its "
+                        "similarities to them; the K - floor(Q (K - 1)) largest are needed, at most 1024")
+    p.add_argument("--neg-groups", default=100, type=int, metavar="G",
+                   help="--score neglabel: the kept words are cut into min(G, M) consecutive groups of floor(M / G); 1..1024")
+    p.add_argument("--neg-T", default=0.01, type=float, help="--score neglabel: the softmax temperature (--T is ignored there)")
     args = p.parse_args(argv)
+    if args.score == "neglabel":
+        if not args.neg_words:
+            p.error("--score neglabel needs --neg-words FILE (one candidate word per line)")
+        if args.neg_count < 0 or not 0.0 < args.neg_frac <= 1.0 or not 0.0 <= args.neg_quantile <= 1.0:
+            p.error("--neg-count must be >= 0, --neg-frac in (0, 1], --neg-quantile in [0, 1]")
+        if not 1 <= args.neg_groups <= 1024:
+            p.error("--neg-groups G: G must be 1..1024")
+        if not (args.neg_T > 0.0 and np.isfinite(args.neg_T)):
+            p.error("--neg-T must be positive and finite")
     if not 0 <= args.knn_k <= 1024:
         p.error("--knn-k K: K must be 1..1024 (0 = chosen from the bank size)")
-    if args.score == "knn" and args.refine_threshold in ("on", "exact"):
+    if args.score in ("knn", "neglabel") and args.refine_threshold in ("on", "exact"):
         p.error("--refine-threshold on needs a 16-bit --dtype and an MCM-family --score")
     if args.maha_fit == "device" and args.score != "maha":
         p.error("--maha-fit device needs --score maha (no other score fits anything)")
@@ -132,6 +154,8 @@ def process_args(argv=None):
         if args.score in ("maha", "knn"):
             p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the training-set "
                     "baselines (--score maha, --score knn) have no prompt bank to match against")
+        if args.score == "neglabel":
+            p.error("--predict is not available with --score neglabel (its kernel returns group masses, not matched concepts)")
         if not 1 <= args.predict <= 8:
             p.error("--predict K: K must be 1..8")
     if args.decoder:
@@ -267,7 +291,9 @@ def main(argv=None):
     # the split-activation workspace of an fp16 handle (include/mcm.h mcm_config.x2_max_batch): the whole run goes
     # through that arm with --dtype fp16x2 (full batch: twice the activation bytes); threshold refinement re-scores a few hundred
     # images, for which half the batch costs nothing extra; otherwise the workspace is not allocated at all
-    no_bank = args.score in ("maha", "knn")   # the training-set baselines: no prompt bank, scores come back as host arrays
+    # the training-set baselines (no prompt bank) and neglabel (a bank of its own): scores come back as host arrays, and
+    # there is no threshold refinement
+    no_bank = args.score in ("maha", "knn", "neglabel")
     will_refine = args.refine_threshold != "off" and not no_bank
     x2_batch = 0 if args.dtype == "fp16x2" else (max(1, args.batch_size // 2) if (args.dtype == "fp16" and will_refine) else -1)
     net = build_model(args.CLIP_ckpt, weights=args.weights, device=dev, precision=args.dtype,
@@ -344,6 +370,17 @@ def main(argv=None):
         log.debug(f"--score knn: k = {knn_k}{'' if args.knn_k else ' (auto)'}, bank of {len(knn_bank)} unit-norm training features "
                   f"x {knn_bank.shape[1]} ({sources['train']['kind']})")
         in_score = get_knn_score(args, net, test_loader, knn_bank, knn_k)
+    elif args.score == "neglabel":
+        from mcm_amd.detection import get_neglabel_bank, get_neglabel_score
+
+        with open(args.neg_words, encoding="utf-8") as f:
+            neg_words = f.read().splitlines()
+        log.debug(f"--score neglabel: --T {args.T} is ignored; the softmax temperature is --neg-T {args.neg_T}")
+        neg_bank = get_neglabel_bank(args, net, test_labels, neg_words)
+        log.debug(f"--score neglabel: K = {neg_bank['K']} ID labels, C = {neg_bank['C']} candidate words from {args.neg_words}, "
+                  f"M = {neg_bank['M']} kept, G = {neg_bank['G']} groups of gs = {neg_bank['gs']}; kept d from "
+                  f"{float(neg_bank['d'].min()):.6f} to {float(neg_bank['d'].max()):.6f} (quantile {args.neg_quantile})")
+        in_score = get_neglabel_score(args, net, test_loader, neg_bank)
     else:
         in_score = _score_set(args, net, test_loader, test_labels, "id", log, rank, on_dev, in_dist=True)
         _note_pillow_files(net, sources, "id", log)
@@ -387,6 +424,8 @@ def main(argv=None):
             out_score = get_Mahalanobis_score(args, net, ood_loader, classwise_mean, precision, in_dist=False)
         elif args.score == "knn":
             out_score = get_knn_score(args, net, ood_loader, knn_bank, knn_k)
+        elif args.score == "neglabel":
+            out_score = get_neglabel_score(args, net, ood_loader, neg_bank)
         else:
             out_score = _score_set(args, net, ood_loader, test_labels, out_dataset, log, rank, on_dev)
             _note_pillow_files(net, sources, out_dataset, log)

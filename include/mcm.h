@@ -42,7 +42,8 @@ extern "C" {
                           * (still 5) mcm_score_features_topk / mcm_score_topk: two added symbols, no struct, constant or
                           * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged
                           * (still 5) mcm_maha_fit_accumulate: an added symbol, on the same terms
-                          * (still 5) mcm_knn_workspace_bytes / mcm_knn_score_features: two added symbols, on the same terms */
+                          * (still 5) mcm_knn_workspace_bytes / mcm_knn_score_features: two added symbols, on the same terms
+                          * (still 5) mcm_neglabel_workspace_bytes / mcm_neglabel_score_features: two added symbols, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -399,6 +400,43 @@ int mcm_knn_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim
                            const float* bank_dev /* [N, proj_dim] */, int64_t N, int32_t k, int32_t splits,
                            void* work_dev, int64_t work_bytes, float* scores_dev /* [B] */,
                            float* topv_dev /* [B, k] or NULL */, void* stream);
+
+/* ---- negative-label score (--score neglabel; Jiang et al., ICLR 2024) --------------------------------
+ * The share of a feature row's softmax mass that falls on the in-distribution (ID) prompts of a bank that also holds
+ * mined negative prompts (added under ABI 5: two symbols only).  P = the handle's proj_dim, everything row-major:
+ *   bank_dev [N, P]  rows [0, K) are the ID prompts, rows [K + g gs, K + (g + 1) gs) are negative group g of G;
+ *                    N = K + G gs, which must fit int32;
+ *   s[b, n]          = the fp32 dot product of feats_dev[b] and bank_dev[n] as mcm_knn_score_features defines it (the
+ *                    exact-fp32 MFMA: one rounding per product, operands never narrowed);
+ *   LI[b]            = logsumexp_n s[b, n] / T over the ID rows, LN[b, g] = the same over group g;
+ *   S[b, g]          = 1 / (1 + exp(LN[b, g] - LI[b])): the ID mass against group g alone (finite for finite inputs);
+ *   scores[b]        = -(1 / G) sum_g S[b, g], summed in fp64 over the fp32 values group_dev gets; larger = more OOD, the
+ *                    sign every stored score here has;
+ *   group_dev[b, g]  = S[b, g] (optional).
+ * A NaN similarity anywhere in a row makes that row's score NaN (as a softmax would); other rows are unaffected.
+ * The [B, N] similarities exist in registers and LDS only.  The bank is cut into `splits` contiguous ranges of
+ * ceil(N / splits) rows (the last ones may be short or empty); each keeps one online-softmax pair (max, sum of
+ * exp((s - max) / T); the sum carried in fp64, stored as fp32) per query and per row range (the ID rows, or one group)
+ * it holds rows of in work_dev ([splits, B, G + 1] pairs of 8 bytes); a second launch combines them in split order in
+ * fp64.  Only the slots the first launch wrote are read (which those are follows from K, gs and the split length), so
+ * work_dev needs no initialisation.  splits = 0: the library chooses from B, N and the device's CU count; n > 0:
+ * exactly n, at most MCM_KNN_MAX_SPLITS.  For fixed arguments (splits included) the outputs are the same bits on every
+ * run, for every cut of the queries into calls and every row position (no atomics, no workgroup waits for another);
+ * across `splits` the sums are associated differently and the results agree to rounding, not bit for bit.
+ * mcm_neglabel_workspace_bytes: *bytes_out = the work_dev size the score call needs for the same (B, K, G, gs, splits);
+ * with splits = 0 it resolves the split count on the CURRENT device, as the score call does.
+ * Asynchronous on `stream`, no allocation, no host synchronisation; timed under MCM_KC_SCORE (2 B N P flop).
+ * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
+ * B, K, G or gs < 1, G > MCM_NEG_MAX_GROUPS, T <= 0 or not finite, splits < 0 or > MCM_KNN_MAX_SPLITS, work_bytes below
+ * mcm_neglabel_workspace_bytes, proj_dim % 4 != 0, feats_dev / bank_dev not 16-byte aligned, or K + G gs above
+ * INT32_MAX.  group_dev may be NULL. */
+#define MCM_NEG_MAX_GROUPS 1024
+int mcm_neglabel_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits,
+                                 int64_t* bytes_out);
+int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
+                                const float* bank_dev /* [K + G gs, proj_dim] */, int32_t K, int32_t G, int32_t gs,
+                                float T, int32_t splits, void* work_dev, int64_t work_bytes,
+                                float* scores_dev /* [B] */, float* group_dev /* [B, G] or NULL */, void* stream);
 
 /* ---- CLIP byte-level BPE tokenizer, host side --------------------------------
  * Replaces CLIPTokenizer.from_pretrained(args.ckpt) + tokenizer(list[str], padding=True,

@@ -430,6 +430,13 @@ int knn_auto_splits(int B, int64_t N);
 hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, int P, int k, int S, float* work,
                       float* scores, float* topv, hipStream_t s);
 
+// neglabel.hip: the NegLabel score of every feats row against bank [K + G gs, P] (rows [0, K) the ID prompts, then G
+// groups of gs negatives): scores [B] = -(1/G) sum_g S[b, g], group [B, G] (or nullptr) = S, the ID softmax mass against
+// group g alone at temperature T.  work holds neglabel_work_bytes(B, G, S): one (max, sum) pair per (split, query, range).
+int64_t neglabel_work_bytes(int B, int G, int S);
+hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, int G, int gs, int P, float T, int S,
+                           void* work, float* scores, float* group, hipStream_t s);
+
 hipError_t launch_score(const float* img, int B, const float* text, int K, int P, float T,
                         int kind, float* scores, hipStream_t s);
 // the top-k form of the same tail (score_kernel<true>): idx [B,topk] int32, prob [B,topk] fp32 or nullptr;

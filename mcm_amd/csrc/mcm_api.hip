@@ -866,6 +866,43 @@ int mcm_knn_score_features(mcm_handle* h, const float* feats_dev, int32_t B, con
   return MCM_OK;
 }
 
+namespace {
+// the argument rules both NegLabel entries share; *S_out = the split count the call runs with
+int neglabel_check(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits, int* S_out) {
+  if (B < 1 || K < 1 || G < 1 || G > MCM_NEG_MAX_GROUPS || gs < 1 || splits < 0 || splits > MCM_KNN_MAX_SPLITS)
+    return MCM_EINVAL;
+  if ((int64_t)K + (int64_t)G * gs > INT32_MAX) return MCM_EINVAL;
+  if (h->cfg.proj_dim < 4 || h->cfg.proj_dim % 4) return MCM_EINVAL;
+  *S_out = splits ? splits : knn_auto_splits(B, (int64_t)K + (int64_t)G * gs);
+  return MCM_OK;
+}
+}  // namespace
+
+int mcm_neglabel_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits,
+                                 int64_t* bytes_out) {
+  int S = 0;
+  if (!h || !bytes_out || neglabel_check(h, B, K, G, gs, splits, &S)) return MCM_EINVAL;
+  *bytes_out = neglabel_work_bytes(B, G, S);
+  return MCM_OK;
+}
+
+int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev, int32_t B, const float* bank_dev, int32_t K,
+                                int32_t G, int32_t gs, float T, int32_t splits, void* work_dev, int64_t work_bytes,
+                                float* scores_dev, float* group_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  int S = 0;
+  if (!feats_dev || !bank_dev || !work_dev || !scores_dev || neglabel_check(h, B, K, G, gs, splits, &S))
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (((uintptr_t)feats_dev | (uintptr_t)bank_dev) & 15) return fail(h, MCM_EINVAL, "feats_dev / bank_dev must be 16-byte aligned");
+  if (work_bytes < neglabel_work_bytes(B, G, S))
+    return fail(h, MCM_EINVAL, "work_bytes is below mcm_neglabel_workspace_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * ((double)K + (double)G * gs) * h->cfg.proj_dim);
+  HIP_TRY(h, launch_neglabel(feats_dev, B, bank_dev, K, G, gs, h->cfg.proj_dim, T, S, work_dev, scores_dev, group_dev, s));
+  return MCM_OK;
+}
+
 int mcm_encode_image_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, float* out_dev,
                         void* stream) {
   return encode_image_impl(h, pixels_dev, true, B, out_dev, stream);

@@ -528,6 +528,147 @@ def get_knn_score(args, net, loader, bank, k):
     return res.detach().cpu().numpy().astype(np.float32)[:n_total]
 
 
+NEG_MAX_GROUPS = 1024  # MCM_NEG_MAX_GROUPS of include/mcm.h
+
+
+def clean_negative_words(words, id_names):
+    """Step 1 of the mining: the candidate words in file order, stripped; empty lines, later duplicates and words equal to an ID
+    class name are dropped (all comparisons case-insensitive)."""
+    seen = {str(c).strip().lower() for c in id_names}
+    out = []
+    for w in words:
+        w = str(w).strip()
+        if w and w.lower() not in seen:
+            seen.add(w.lower())
+            out.append(w)
+    return out
+
+
+def _candidate_features(args, net, cands):
+    """[C, P] unit-norm fp32 text features of the candidate words through the ID labels' prompt template, on every rank: each
+    rank encodes its `shard_range` of the candidates and the rows are all-gathered, as `get_knn_bank` does for images.  The
+    whole list is tokenised on every rank, so a row's padded length does not depend on the world size."""
+    import torch
+
+    rank, ws = mdist.world()
+    C = len(cands)
+    lo, hi = mdist.shard_range(C, rank, ws) if ws > 1 else (0, C)
+    templates = getattr(args, "templates", None)
+    with torch.no_grad():
+        if hi <= lo:
+            local = None
+        elif templates:
+            local = encode_prompt_ensemble(args, net, cands[lo:hi], templates)
+        else:
+            tok = _tokenizer(args, net)([PROMPT.format(c=c) for c in cands], padding=True, return_tensors="pt")
+            local = _unit_text_features(net, {"input_ids": tok["input_ids"][lo:hi], "attention_mask": tok["attention_mask"][lo:hi]})
+        if local is None:
+            P = getattr(getattr(net, "geo", None), "proj_dim", None) or getattr(args, "feat_dim", 0)
+            local = torch.empty((0, int(P)), dtype=torch.float32, device=getattr(net, "device", None) or "cpu")
+        local = local.float()
+        if mdist.group_active():
+            local = mdist.all_gather_rows(local.contiguous(), C)
+    return local.detach()[:C].contiguous()
+
+
+def _mine(args, net, id_names, words):
+    """The mining of `mine_negative_labels`, with everything `get_neglabel_bank` needs next to it."""
+    import torch
+
+    if not hasattr(net, "knn_scores"):
+        raise TypeError("mining negative labels needs a net with knn_scores (a NativeCLIP); there is no eager fallback")
+    id_names = list(id_names)
+    K = len(id_names)
+    cands = clean_negative_words(words, id_names)
+    C = len(cands)
+    if K < 1 or C < 1:
+        raise ValueError(f"--score neglabel: {K} ID names and {C} candidate words are left after cleaning; both must be at least 1")
+    q = float(getattr(args, "neg_quantile", 0.95))
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"--neg-quantile {q}: must lie in [0, 1]")
+    h = q * (K - 1)
+    lo = int(np.floor(h))
+    k = K - lo
+    if k > 1024:
+        raise ValueError(f"--score neglabel: the {q} quantile over {K} ID labels needs the {k} largest similarities of every "
+                         "candidate, and knn_scores returns at most 1024: raise --neg-quantile")
+    id_bank = prompt_bank(args, net, id_names)
+    cand = _candidate_features(args, net, cands)
+    with torch.no_grad():
+        _, topv = net.knn_scores(cand, id_bank, k, return_values=True)
+    topv = topv.detach().cpu().numpy().astype(np.float64)
+    a_lo, a_hi = topv[:, K - 1 - lo], topv[:, max(K - 2 - lo, 0)]
+    d = a_lo + (h - lo) * (a_hi - a_lo)
+    count = int(getattr(args, "neg_count", 0) or 0)
+    M = count if count > 0 else int(round(float(getattr(args, "neg_frac", 0.15)) * C))
+    M = min(M, C)
+    if M < 1:
+        raise ValueError(f"--score neglabel: no candidate is kept (--neg-count / --neg-frac select {M} of {C})")
+    order = np.lexsort((np.arange(C), d))[:M]          # d ascending, candidate index ascending among equals
+    G = min(int(getattr(args, "neg_groups", 100)), M)
+    if not 1 <= G <= NEG_MAX_GROUPS:
+        raise ValueError(f"--neg-groups: {G} groups; 1 .. {NEG_MAX_GROUPS} are supported")
+    gs = M // G
+    order = order[:G * gs]
+    return {"words": [cands[i] for i in order], "d": d[order], "index": order, "cand": cand, "id_bank": id_bank,
+            "K": K, "C": C, "M": M, "G": G, "gs": gs}
+
+
+def mine_negative_labels(args, net, id_names, words):
+    """NegLabel's mining (Jiang et al., ICLR 2024): from the candidate `words` keep the ones farthest from the ID labels.
+    d[c] = the `args.neg_quantile` (default 0.95) quantile, linearly interpolated, of candidate c's similarities to the K ID
+    prompts, from the device's top-k values (`net.knn_scores(..., return_values=True)`) and finished in fp64; the
+    M = `args.neg_count`, or round(`args.neg_frac` (0.15) x C), candidates with the smallest d are kept, ordered by (d, index),
+    cut into G = min(`args.neg_groups` (100), M) consecutive groups of gs = M // G; the last M - G gs are dropped.
+    Returns (the G gs selected words in that order, their d as a float64 ndarray)."""
+    m = _mine(args, net, id_names, words)
+    return m["words"], m["d"]
+
+
+def get_neglabel_bank(args, net, id_names, words):
+    """`--score neglabel`: the bank [K + G gs, P] of unit-norm fp32 text features — the K ID prompts, then the mined negatives
+    group after group — with its geometry: {"bank", "K", "G", "gs", "words", "d", "C", "M"}.  Replicated on every rank, and
+    the same bits at every world size (every rank mines the same gathered candidate features)."""
+    import torch
+
+    m = _mine(args, net, id_names, words)
+    idx = torch.as_tensor(np.ascontiguousarray(m["index"]), dtype=torch.long, device=m["cand"].device)
+    bank = torch.cat([m["id_bank"].float().to(m["cand"].device), m["cand"].index_select(0, idx)]).contiguous()
+    return {"bank": bank, "K": m["K"], "G": m["G"], "gs": m["gs"], "words": m["words"], "d": m["d"], "C": m["C"], "M": m["M"]}
+
+
+def get_neglabel_score(args, net, loader, bank_info):
+    """`--score neglabel`: per sample -(1/G) sum_g S_g, S_g the softmax mass at temperature `args.neg_T` (0.01) of its unit-norm
+    feature on the ID prompts against negative group g alone (`net.neglabel_scores`); larger = more OOD.  Sharded and gathered
+    like `get_knn_score`; EVERY sample is scored.  Returns a float32 ndarray [len(loader.dataset)]."""
+    import torch
+
+    if not hasattr(net, "neglabel_scores"):
+        raise TypeError("get_neglabel_score needs a net with neglabel_scores (a NativeCLIP); there is no eager fallback")
+    bank, K, G, gs = bank_info["bank"], int(bank_info["K"]), int(bank_info["G"]), int(bank_info["gs"])
+    T = float(getattr(args, "neg_T", 0.01))
+    rank, ws = mdist.world()
+    n_total = len(loader.dataset)
+    batches, lo, hi = loader, 0, n_total
+    if ws > 1:
+        lo, hi = mdist.shard_range(n_total, rank, ws)
+        batches = shard_loader(loader, lo, hi)
+        if batches is None:
+            raise TypeError("--score neglabel under world_size > 1 needs a loader that can be sharded by index")
+    out, seen = [], 0
+    with torch.no_grad():
+        for images, _labels in (batches if hi > lo else ()):
+            if seen >= hi - lo:
+                break
+            f = _unit_image_features(net, images[: hi - lo - seen])
+            out.append(net.neglabel_scores(f, bank, K, G, gs, T=T))
+            seen += f.shape[0]
+    res = torch.cat(out) if out else torch.empty(0, dtype=torch.float32, device=bank.device)
+    if mdist.group_active():
+        res = mdist.all_gather_scores(res, n_total)
+    return res.detach().cpu().numpy().astype(np.float32)[:n_total]
+
+
 def _gather_batch_shards(local, n_total, ws):
     """All-gather score shards whose sizes only the owning rank knows (batch-range split of a generic
     loader: the last batch may be short, batch sizes need not be uniform).  Counts are exchanged first;

@@ -148,6 +148,8 @@ def load_library(harness: bool = False):
     L.mcm_maha_fit_accumulate.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.mcm_knn_workspace_bytes.argtypes = [vp, i32, ctypes.c_int64, i32, i32, ctypes.POINTER(ctypes.c_int64)]
     L.mcm_knn_score_features.argtypes = [vp, vp, i32, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
+    L.mcm_neglabel_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
+    L.mcm_neglabel_score_features.argtypes = [vp, vp, i32, vp, i32, i32, i32, ctypes.c_float, i32, vp, ctypes.c_int64, vp, vp, vp]
     L.mcm_measures.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, ctypes.c_double,
                                ctypes.POINTER(ctypes.c_double), vp]
     L.mcm_saturation_check.argtypes = [vp, i32]
@@ -175,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "mcm_score_features_topk", "mcm_score_topk",
     "mcm_maha_fit_accumulate",
     "mcm_knn_workspace_bytes", "mcm_knn_score_features",
+    "mcm_neglabel_workspace_bytes", "mcm_neglabel_score_features",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -391,6 +394,47 @@ class NativeCLIP:
         if rc:
             raise ValueError(f"knn_scores: refused (rc={rc}) for B={B}, N={N}, k={k}, splits={splits}: B >= 1, N >= 1, "
                              "1 <= k <= 1024, 0 <= splits <= 32 and proj_dim % 4 == 0 are required")
+
+    def neglabel_scores(self, features, bank, n_id, groups, group_size, T: float = 0.01, splits: int = 0,
+                        return_groups: bool = False):
+        """features [B,P], bank [n_id + groups * group_size, P] fp32 (device) → [B] fp32: the NegLabel score -(1/G) sum_g S_g,
+        S_g = 1 / (1 + exp(LN_g - LI)) the softmax mass at temperature T of the bank's first n_id rows (the ID prompts) against
+        negative group g alone (include/mcm.h mcm_neglabel_score_features); larger = more OOD.  `splits`: 0 = the library's
+        choice, n = the bank in exactly n ranges (results agree across it to rounding, and are the same bits for a fixed
+        value).  `return_groups=True`: (scores, S [B,groups]).  The workspace is a buffer of this object that grows on
+        demand; queries go through in blocks of at most 4096 rows."""
+        import torch
+
+        f = features.to(device=self.device, dtype=torch.float32).contiguous()
+        bk = bank.to(device=self.device, dtype=torch.float32).contiguous()
+        P, K, G, gs, splits, T = self.geo.proj_dim, int(n_id), int(groups), int(group_size), int(splits), float(T)
+        if f.dim() != 2 or f.shape[1] != P or bk.dim() != 2 or bk.shape[1] != P:
+            raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
+        if K < 1 or G < 1 or gs < 1 or bk.shape[0] != K + G * gs:
+            raise ValueError(f"neglabel_scores: the bank has {bk.shape[0]} rows, n_id + groups * group_size = {K} + {G} * {gs}")
+        B = int(f.shape[0])
+        scores = torch.empty(B, device=self.device, dtype=torch.float32)
+        grp = torch.empty((B, G), device=self.device, dtype=torch.float32) if return_groups else None
+        for s in range(0, max(B, 1), 4096):
+            n = min(4096, B - s)
+            need = ctypes.c_int64(0)
+            self._check_neglabel(self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, ctypes.byref(need)),
+                                 n, K, G, gs, T, splits)
+            work = getattr(self, "_neg_work", None)
+            if work is None or work.numel() * 4 < need.value:
+                work = self._neg_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+            self._check_neglabel(self._lib.mcm_neglabel_score_features(
+                self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, G, gs, T, splits, work.data_ptr(), work.numel() * 4,
+                scores[s:s + n].data_ptr(), grp[s:s + n].data_ptr() if return_groups else None, _stream_ptr()),
+                n, K, G, gs, T, splits)
+        return (scores, grp) if return_groups else scores
+
+    def _check_neglabel(self, rc, B, K, G, gs, T, splits):
+        if rc == -1:
+            raise ValueError(f"neglabel_scores: refused (rc={rc}) for B={B}, n_id={K}, groups={G}, group_size={gs}, T={T}, "
+                             f"splits={splits}: B, n_id, group_size >= 1, 1 <= groups <= 1024, T > 0 and finite, "
+                             "0 <= splits <= 32 and proj_dim % 4 == 0 are required")
+        self._check(rc)
 
     def get_text_features(self, input_ids, attention_mask=None, normalize: bool = False):
         """[K,S] ids → [K,P] fp32: HF `get_text_features` (the text projection output; unit-norm rows
