@@ -16,7 +16,7 @@
 // contributing row is recomputed, rounded to uint8 exactly as the intermediate image would hold
 // it), so there is no intermediate image and nothing is allocated.
 // Two forms in one kernel, chosen per workgroup (8 output rows of one image), same integer arithmetic:
-//   LDS form (round 4)   filters of at most 16 taps per axis (scale factors up to 7.5) whose working set fits the LDS budget.
+//   LDS form (round 4)   filters of at most 16 taps per axis (2 * ceil(scale) + 1: scale factors up to 7) whose working set fits the LDS budget.
 //                        A prologue kernel computes each image's coefficient tables once (zero-padded to 8 / 16 taps); a
 //                        workgroup stages the source window of its rows (of 8, 4, 2 or 1 of them at a time, whichever fits)
 //                        into LDS with 16-byte loads, runs the horizontal pass once per staged row into an LDS copy of
@@ -37,6 +37,7 @@ constexpr int KMAX = 64;    // taps per output coordinate: 2*ceil(scale)+1 -> sc
 constexpr int ROWS = 8;     // output rows per workgroup
 constexpr int FT = 16;      // LDS form: taps per output coordinate it holds
 constexpr int LDS_FORM_BYTES = 56 * 1024;  // LDS form: staged source window + horizontal-pass rows (two workgroups per CU)
+// (the form choice below — taps, rows per pass, window stride, this budget — is mirrored by tests/resize_forms.py form_branches(): change both)
 
 #pragma clang fp contract(off)
 // Resample.c precompute_coeffs + normalize_coeffs_8bpc for output coordinate xx (bilinear)

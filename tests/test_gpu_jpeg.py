@@ -12,7 +12,7 @@ torch = pytest.importorskip("torch")
 PIL = pytest.importorskip("PIL")
 from PIL import Image  # noqa: E402
 
-from tests.test_jpeg_oracle import CASES, _photo, entropy_decode  # noqa: E402
+from tests.test_jpeg_oracle import CASES, _hostile_cases, _photo, entropy_decode, hostile_files  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -160,5 +160,43 @@ def test_reconstruction_with_an_odd_max_batch(tmp_path):
         got = rgb.cpu().numpy()
         for i, a in enumerate(want):
             np.testing.assert_array_equal(got[offs[i]: offs[i] + a.size].reshape(a.shape), a)
+    finally:
+        net.close()
+
+
+def test_hostile_content_reconstruction_equals_pillow(tmp_path):
+    """Constant, saturated and alternating 0 / 255 images (tests/test_jpeg_oracle.py::hostile_files: 7 sizes x 7 contents x
+    quality 1 / 50 / 100 x three samplings x baseline / progressive = 882 files) through jpeg.hip in three batches of 294:
+    Pillow's bytes, and the 16 guard bytes between images untouched.  What the narrow sizes reach in jpeg_colour_kernel, by
+    the width of a subsampled chroma plane, dw = (width + 1) >> 1: (33, 3) and (9, 4) have dw = 2 and (21, 1) has dw = 1, the
+    replication rule (`dw <= 2`, with its min(.., dw - 1)); (33, 7) has dw = 4, the narrowest filtered plane, its first and
+    last chroma column in the same, ragged, group of eight pixels; (16, 250) ends each row in a ragged group of two pixels
+    on the last chroma column."""
+    from mcm_amd.config import geometry
+    from mcm_amd.engine import NativeCLIP
+    from mcm_amd.weights import synth_state_dict
+
+    paths = [p for h, w, kind in _hostile_cases() for p in hostile_files(tmp_path, h, w, kind)]
+    assert len(paths) == 882
+    geo = geometry("tiny")   # the towers never run
+    net = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=294, max_prompt_tokens=1024)
+    try:
+        for k in range(0, len(paths), net.max_batch):
+            batch = paths[k:k + net.max_batch]
+            meta, quant, buf = entropy_decode(batch, threads=4)
+            assert all(m.status == 0 for m in meta) and len(batch) == 294
+            want = [_pil(p) for p in batch]
+            offs, o = [], 16
+            for a in want:
+                offs.append(o)
+                o += (a.size + 15) // 16 * 16 + 16
+            rgb = torch.full((o,), 7, dtype=torch.uint8, device="cuda")
+            net.jpeg_reconstruct(torch.from_numpy(buf).cuda(), meta, quant, len(batch), rgb, offs)
+            got = rgb.cpu().numpy()
+            taken = np.zeros(o, dtype=bool)
+            for i, a in enumerate(want):
+                np.testing.assert_array_equal(got[offs[i]: offs[i] + a.size].reshape(a.shape), a, err_msg=os.path.basename(batch[i]))
+                taken[offs[i]: offs[i] + a.size] = True
+            assert (got[~taken] == 7).all(), "bytes outside the images were written"
     finally:
         net.close()

@@ -109,7 +109,7 @@ def test_full_tower_vs_hf_and_the_split_arm(full_tower):
 
 def test_uint8_ingest_at_336(full_tower):
     """Odd-sized uint8 images through the device Resize(336) + CenterCrop(336) (mcm_resize_crop_u8) and the fused
-    ToTensor / Normalize: the same scores as the float route on the same crops."""
+    ToTensor / Normalize: the crops are the oracle's, and the scores those of the float route on the same crops."""
     geo, sd, ids, mask = full_tower
     rng = np.random.default_rng(11)
     imgs = [torch.from_numpy(rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)) for h, w in
@@ -119,6 +119,10 @@ def test_uint8_ingest_at_336(full_tower):
         bank = net.get_text_features(input_ids=torch.from_numpy(ids), attention_mask=torch.from_numpy(mask), normalize=True)
         u8 = net.resize_crop(imgs)
         assert tuple(u8.shape) == (5, 336, 336, 3)
+        from oracle import oracle as orc
+
+        for im, crop in zip(imgs, u8.cpu().numpy()):   # the crops themselves: Pillow's bytes (the oracle's, bit for bit)
+            np.testing.assert_array_equal(crop, orc.resize_crop_u8(im.numpy(), 336), err_msg=str(tuple(im.shape)))
         f32 = ((u8.cpu().numpy().astype(np.float32) / np.float32(255.0) - MEAN) / STD).transpose(0, 3, 1, 2).copy()
         s_u8 = net.score_images(u8, bank).double()
         s_f = net.score_images(torch.from_numpy(f32).cuda(), bank).double()

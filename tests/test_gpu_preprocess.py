@@ -1,5 +1,8 @@
 """mcm_resize_crop_u8 vs Pillow's outputs (tests/golden/preprocess.npz) and the C
-oracle: integer work, so every comparison is bit-exact."""
+oracle: integer work, so every comparison is bit-exact.  Everything here runs at crop size S = 224 on random bytes, with the
+shipped form choice.  The other crop sizes (64, 336, and 70 / 84 for the row-group tails), every branch of the form choice
+per S, the fused form forced on LDS-form images, constant / saturated / alternating content, packed sources at 336 and 84
+and the staging ring are tests/test_gpu_preprocess_sizes.py's."""
 import hashlib
 import os
 
@@ -52,8 +55,9 @@ def test_random_sizes_match_oracle(net):
     rng = np.random.default_rng(11)
     sizes = [(int(rng.integers(20, 900)), int(rng.integers(20, 900))) for _ in range(24)]
     sizes += [(224, 224), (224, 301), (299, 224), (1, 1), (2, 700), (448, 448)]
-    # every branch of the kernel's form choice (preprocess.hip): 8-tap tables with 8 / 4 / 2 rows per LDS pass, 16-tap tables
-    # with 1 row per pass, a window that fits no pass (fused form), more than 16 taps (fused form), upscaling
+    # branches of the kernel's form choice (preprocess.hip) at S = 224: 8-tap tables with 8 / 4 rows per LDS pass (2 do not occur
+    # at 224: tests/test_resize_forms.py), 16-tap tables down to 1 row per pass, a window that fits no pass (fused form), more
+    # than 16 taps (fused form), upscaling.  tests/test_gpu_preprocess_sizes.py runs tables proven to reach every branch.
     sizes += [(375, 500), (600, 800), (768, 1024), (1200, 1600), (1600, 1200), (2000, 1500), (1800, 4000), (120, 160), (230, 229)]
     imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in sizes]
     out = np.concatenate([net.resize_crop([_dev(i) for i in imgs[k:k + 20]]).cpu().numpy() for k in range(0, len(imgs), 20)])

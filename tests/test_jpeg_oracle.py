@@ -79,6 +79,47 @@ def test_entropy_decode_plus_reference_reconstruction_equals_pillow(tmp_path, ca
     np.testing.assert_array_equal(got, want)
 
 
+# Subsampled chroma planes are dw = (width + 1) >> 1 samples wide: 32, 66, 4 and 125 here, then 2, 2 and 1.  (33, 7) is the first
+# width libjpeg filters (dw = 4: first and last chroma column in one group of eight pixels, which is also the ragged last
+# group); (33, 3), (9, 4) and (21, 1) take the replication rule for dw <= 2 (jdsample.c; jpeg.hip's `dw <= 2` branch) with an odd
+# and an even width at dw = 2 and with dw = 1; (16, 250) ends its rows in a ragged group of two pixels on chroma column 124.
+HOSTILE_SIZES = [(64, 64), (97, 131), (33, 7), (16, 250), (33, 3), (9, 4), (21, 1)]
+HOSTILE_PARAMS = [dict(quality=q, subsampling=s, progressive=p) for q in (1, 50, 100) for s in (0, 1, 2) for p in (False, True)]
+
+
+def hostile_files(dirname, h, w, kind):
+    """The 18 files (quality 1 / 50 / 100 x 4:4:4 / 4:2:2 / 4:2:0 x baseline / progressive) of one size and one content of
+    tests/resize_forms.py: constants, saturated and alternating 0 / 255 pixels drive the IDCT's overshoot and the YCbCr
+    conversion into their clamps, which photo-like content only grazes.  Shared with tests/test_gpu_jpeg.py."""
+    from tests.resize_forms import CONTENT_KINDS, content
+
+    img = content(kind, h, w, np.random.default_rng([h, w, CONTENT_KINDS.index(kind)]))
+    paths = []
+    for kw in HOSTILE_PARAMS:
+        p = os.path.join(str(dirname), f"{kind}_{h}x{w}_q{kw['quality']}_s{kw['subsampling']}_{'p' if kw['progressive'] else 'b'}.jpg")
+        Image.fromarray(img).save(p, **kw)
+        paths.append(p)
+    return paths
+
+
+def _hostile_cases():
+    from tests.resize_forms import CONTENT_KINDS
+
+    return [(h, w, kind) for h, w in HOSTILE_SIZES for kind in CONTENT_KINDS]
+
+
+@pytest.mark.parametrize("h,w,kind", _hostile_cases())
+def test_hostile_content_entropy_decode_plus_reference_reconstruction_equals_pillow(tmp_path, h, w, kind):
+    paths = hostile_files(tmp_path, h, w, kind)
+    assert len(paths) == 18
+    meta, quant, buf = entropy_decode(paths)
+    for i, p in enumerate(paths):
+        assert meta[i].status == 0 and (meta[i].height, meta[i].width) == (h, w), os.path.basename(p)
+        with Image.open(p) as im:
+            want = np.asarray(im.convert("RGB"))
+        np.testing.assert_array_equal(reconstruct(meta[i], quant[i], buf), want, err_msg=os.path.basename(p))
+
+
 def test_grayscale_batch_and_files_the_path_does_not_take(tmp_path):
     paths, want = [], []
     for i, (h, w) in enumerate([(100, 130), (64, 64), (97, 31)]):
