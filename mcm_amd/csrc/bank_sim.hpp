@@ -1,0 +1,134 @@
+// bank_sim.hpp — the bank walk of the bank-streamed scores (knn.hip, neglabel.hip): a workgroup of 256
+// threads takes 64 query rows and a range of bank rows and sees the exact-fp32 similarities 64 x 256 at a time in LDS,
+// without the [B, N] matrix ever existing in HBM.  A score is what its kernel does with a tile (the callback of walk)
+// and the state it keeps *behind* the tile: its dynamic LDS is TILE_BYTES plus what it states for itself.
+#pragma once
+#include "common.hpp"
+
+namespace bank_sim {
+constexpr int Q = 64;             // queries of a workgroup
+constexpr int TN = 256;           // bank rows of a tile
+constexpr int KC = 32;            // feature columns of a staged chunk
+constexpr int LDA = KC + 4;       // LDS row stride of a staged operand (floats; rows stay 16-byte aligned)
+constexpr int LDSIM = TN + 4;     // LDS row stride of the similarity tile
+constexpr int THREADS = 256;
+constexpr int STAGE_FLOATS = (Q + TN) * LDA;
+constexpr int SIM_FLOATS = Q * LDSIM;  // the similarity tile lies over the staging buffers (they are dead by then)
+constexpr int TILE_BYTES = SIM_FLOATS * (int)sizeof(float);  // a score's own LDS starts here
+static_assert(STAGE_FLOATS <= SIM_FLOATS, "the staging buffers must fit under the similarity tile");
+
+// split s of a bank of N rows cut into ranges of `per` rows holds rows [lo, hi) = [s per, min(N, (s + 1) per))
+__device__ __forceinline__ void split_bounds(int64_t s, int64_t per, int64_t N, int64_t& lo, int64_t& hi) {
+  lo = s * per < N ? s * per : N;
+  hi = lo + per < N ? lo + per : N;
+}
+
+// Walks bank rows [lo, hi) in tiles of TN for the nq <= Q query rows from q0 (feats [B, P], bank [N, P], P % 4 == 0, both
+// 16-byte aligned).  Per tile: the Q x TN similarities are accumulated by the exact-fp32 MFMA, both operands staged
+// through LDS in KC-column chunks (the next chunk in registers under the MFMAs), and stored to lds[q * LDSIM + j],
+// j < ncols, with PlusZero -0 as +0 (for a score that must not see which of two equal zeros came first); behind a
+// barrier tile(n0, ncols) is called by every thread.  Rows q >= nq and columns j >= ncols hold the similarities of zero
+// rows.  The tile is overwritten after the next barrier all threads reach, which the walk's next turn provides: a
+// callback needs none of its own to be done reading.  s[b, n] is one fixed sum for given rows, wherever the row falls.
+// A callback captures by value: with reference captures knn_partial_kernel came out with other registers and layout.
+template <bool PlusZero, class Tile>
+__device__ __forceinline__ void walk(const float* feats, const float* bank, int P, int q0, int nq, int64_t lo,
+                                     int64_t hi, float* lds, Tile&& tile) {
+  float* As = lds;             // [Q][LDA]
+  float* Bs = lds + Q * LDA;   // [TN][LDA]
+  float* Sim = lds;            // [Q][LDSIM], over As / Bs
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = lane >> 4, r = lane & 15;
+  const int nchunks = (P + KC - 1) / KC;
+  const int ld_row = tid >> 3, ld_c4 = (tid & 7) * 4;  // a thread's share of a chunk: rows ld_row + 32 i, 4 columns
+  for (int64_t n0 = lo; n0 < hi; n0 += TN) {
+    const int ncols = hi - n0 < TN ? (int)(hi - n0) : TN;
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    float4 ra[2], rb[8];
+    auto gload = [&](int kc) {
+      const int col = kc * KC + ld_c4;
+      const bool cok = col < P;  // P % 4 == 0: four columns are in or out together
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = ld_row + 32 * i;
+        ra[i] = (cok && row < nq) ? *(const float4*)(feats + (int64_t)(q0 + row) * P + col) : float4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int row = ld_row + 32 * i;
+        rb[i] = (cok && row < ncols) ? *(const float4*)(bank + (n0 + row) * (int64_t)P + col) : float4{0.f, 0.f, 0.f, 0.f};
+      }
+    };
+    gload(0);
+    for (int kc = 0; kc < nchunks; ++kc) {
+      __syncthreads();  // the chunk (or the similarity tile) under these bytes has been read
+#pragma unroll
+      for (int i = 0; i < 2; ++i) *(float4*)(As + (ld_row + 32 * i) * LDA + ld_c4) = ra[i];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) *(float4*)(Bs + (ld_row + 32 * i) * LDA + ld_c4) = rb[i];
+      __syncthreads();
+      if (kc + 1 < nchunks) gload(kc + 1);  // in flight under the MFMAs
+#pragma unroll
+      for (int sub = 0; sub < KC / 16; ++sub) {
+        // lane (g, r) takes columns 16 sub + 4 g .. + 3 of its rows as one 16-byte read; MFMA t of the four then
+        // multiplies column 16 sub + 4 g + t of both operands: the same column on both sides, so the sum over the
+        // four MFMAs covers the 16 columns once each (in an order of its own, which a dot product may have)
+        f32x4_t av[4], bv[4];
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+          av[mi] = __builtin_bit_cast(f32x4_t, *(const float4*)(As + (mi * 16 + r) * LDA + sub * 16 + g * 4));
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          bv[ni] = __builtin_bit_cast(f32x4_t, *(const float4*)(Bs + (w * 64 + ni * 16 + r) * LDA + sub * 16 + g * 4));
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][t], bv[ni][t], acc[mi][ni], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // every wave is done with As / Bs
+    // D[i = 4 g + e][j = r]: i a query of block mi, j a bank row of this wave's block ni
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = acc[mi][ni][e];
+          Sim[(mi * 16 + 4 * g + e) * LDSIM + w * 64 + ni * 16 + r] = PlusZero && v == 0.f ? 0.f : v;
+        }
+    __syncthreads();
+    tile(n0, ncols);
+  }
+}
+
+// raises a kernel's dynamic-LDS limit on the current device, once per device (`done`: a static of the launcher)
+inline hipError_t lds_limit_once(PerDeviceFlag& done, const void* kernel, int bytes) {
+  if (done.get()) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.set();
+  return e;
+}
+
+inline unsigned query_tiles(int B) { return (unsigned)(((int64_t)B + Q - 1) / Q); }
+}  // namespace bank_sim
+
+// the split count the library picks from B, N and the current device's CU count (splits = 0 of either score)
+inline int bank_auto_splits(int B, int64_t N) {
+  int cus = device_cu_count();
+  if (cus <= 0) cus = 256;
+  const int64_t qtiles = bank_sim::query_tiles(B);
+  const int64_t tiles = (N + bank_sim::TN - 1) / bank_sim::TN;
+  int64_t want = (2 * (int64_t)cus + qtiles - 1) / qtiles;  // two workgroups fit a CU's LDS
+  if (want > tiles) want = tiles;
+  if (want > MCM_KNN_MAX_SPLITS) want = MCM_KNN_MAX_SPLITS;
+  return want < 1 ? 1 : (int)want;
+}

@@ -425,8 +425,7 @@ hipError_t launch_maha_fit(const float* feats, int B, int P, const float* shift,
 
 // knn.hip: the k largest fp32 similarities of every feats row against bank [N, P], sorted descending, into topv [B, k]
 // (or nullptr), and scores [B] = sqrt(max(0, 2 - 2 topv[:, k - 1])); work holds S * B * k floats (the partial lists of
-// the S bank splits).  knn_auto_splits: the S the library picks from N, B and the current device's CU count.
-int knn_auto_splits(int B, int64_t N);
+// the S bank splits; bank_sim.hpp bank_auto_splits: the S the library picks).
 hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, int P, int k, int S, float* work,
                       float* scores, float* topv, hipStream_t s);
 

@@ -1,10 +1,9 @@
 // knn.hip — the deep k-nearest-neighbour score (include/mcm.h mcm_knn_score_features): the k largest
 // fp32 similarities of every query row against a bank of N training features, without the [B, N] matrix ever
 // existing in HBM.  Two launches in stream order:
-//   knn_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows in tiles of 256:
-//                       the 64 x 256 similarities are accumulated by the exact-fp32 MFMA (both operands staged through
-//                       LDS in 32-column chunks), written to LDS, and every query's k-entry list in the caller's
-//                       workspace takes the ones above its threshold (a wave per query; knn_select_row).
+//   knn_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows (bank_sim.hpp:
+//                       the 64 x 256 exact-fp32 similarities of a tile in LDS), and every query's k-entry list in the
+//                       caller's workspace takes the ones above its threshold (a wave per query; knn_select_row).
 //   knn_merge_kernel    one workgroup per query: the S partial lists (S k values, -inf padded to a power of two) are
 //                       sorted in LDS, the first k are the result.
 // Nothing is summed across workgroups and a top-k multiset does not depend on the order its candidates arrive in, so
@@ -12,21 +11,14 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "bank_sim.hpp"
 
 namespace {
 
 namespace knn {
-constexpr int Q = 64;             // queries of a workgroup
-constexpr int TN = 256;           // bank rows of a tile
-constexpr int KC = 32;            // feature columns of a staged chunk
-constexpr int LDA = KC + 4;       // LDS row stride of a staged operand (floats; rows stay 16-byte aligned)
-constexpr int LDSIM = TN + 4;     // LDS row stride of the similarity tile
-constexpr int THREADS = 256;
-constexpr int STAGE_FLOATS = (Q + TN) * LDA;
-constexpr int SIM_FLOATS = Q * LDSIM;  // the similarity tile lies over the staging buffers (they are dead by then)
-constexpr int LDS_BYTES = (SIM_FLOATS + 3 * Q) * (int)sizeof(float);
-static_assert(STAGE_FLOATS <= SIM_FLOATS, "the staging buffers must fit under the similarity tile");
+using namespace bank_sim;
+// behind the tile: threshold, count and minimum's position of every query's list, [Q] each
+constexpr int LDS_BYTES = TILE_BYTES + 3 * Q * (int)sizeof(float);
 constexpr int MERGE_LDS_MAX = MCM_KNN_MAX_SPLITS * MCM_KNN_MAX_K * (int)sizeof(float);  // 128 KiB
 }  // namespace knn
 
@@ -101,22 +93,17 @@ __device__ __forceinline__ void knn_select_row(const float* row, int n, float* l
 __global__ __launch_bounds__(knn::THREADS) void knn_partial_kernel(KnnArgs a) {
   using namespace knn;
   extern __shared__ __attribute__((aligned(16))) float knn_lds[];
-  float* As = knn_lds;             // [Q][LDA]
-  float* Bs = knn_lds + Q * LDA;   // [TN][LDA]
-  float* Sim = knn_lds;            // [Q][LDSIM], over As / Bs
   float* st_th = knn_lds + SIM_FLOATS;
   int* st_cnt = (int*)(st_th + Q);
   int* st_mp = st_cnt + Q;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int g = lane >> 4, r = lane & 15;
   const int q0 = blockIdx.x * Q;
   const int nq = a.B - q0 < Q ? a.B - q0 : Q;
   const int64_t s = blockIdx.y;
-  const int64_t lo = s * a.per < a.N ? s * a.per : a.N;
-  const int64_t hi = lo + a.per < a.N ? lo + a.per : a.N;
-  const int P = a.P, k = a.k;
-  const int nchunks = (P + KC - 1) / KC;
+  int64_t lo, hi;
+  split_bounds(s, a.per, a.N, lo, hi);
+  const int k = a.k;
 
   if (tid < Q) {
     st_th[tid] = -INFINITY;
@@ -125,87 +112,22 @@ __global__ __launch_bounds__(knn::THREADS) void knn_partial_kernel(KnnArgs a) {
   }
   __syncthreads();
 
-  const int ld_row = tid >> 3, ld_c4 = (tid & 7) * 4;  // a thread's share of a chunk: rows ld_row + 32 i, 4 columns
-  for (int64_t n0 = lo; n0 < hi; n0 += TN) {
-    const int ncols = hi - n0 < TN ? (int)(hi - n0) : TN;
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    float4 ra[2], rb[8];
-    auto gload = [&](int kc) {
-      const int col = kc * KC + ld_c4;
-      const bool cok = col < P;  // P % 4 == 0: four columns are in or out together
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = ld_row + 32 * i;
-        ra[i] = (cok && row < nq) ? *(const float4*)(a.feats + (int64_t)(q0 + row) * P + col) : float4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int row = ld_row + 32 * i;
-        rb[i] = (cok && row < ncols) ? *(const float4*)(a.bank + (n0 + row) * (int64_t)P + col) : float4{0.f, 0.f, 0.f, 0.f};
-      }
-    };
-    gload(0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-      __syncthreads();  // the chunk (or the similarity tile) under these bytes has been read
-#pragma unroll
-      for (int i = 0; i < 2; ++i) *(float4*)(As + (ld_row + 32 * i) * LDA + ld_c4) = ra[i];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) *(float4*)(Bs + (ld_row + 32 * i) * LDA + ld_c4) = rb[i];
-      __syncthreads();
-      if (kc + 1 < nchunks) gload(kc + 1);  // in flight under the MFMAs
-#pragma unroll
-      for (int sub = 0; sub < KC / 16; ++sub) {
-        // lane (g, r) takes columns 16 sub + 4 g .. + 3 of its rows as one 16-byte read; MFMA t of the four then
-        // multiplies column 16 sub + 4 g + t of both operands: the same column on both sides, so the sum over the
-        // four MFMAs covers the 16 columns once each (in an order of its own, which a dot product may have)
-        f32x4_t av[4], bv[4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-          av[mi] = __builtin_bit_cast(f32x4_t, *(const float4*)(As + (mi * 16 + r) * LDA + sub * 16 + g * 4));
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          bv[ni] = __builtin_bit_cast(f32x4_t, *(const float4*)(Bs + (w * 64 + ni * 16 + r) * LDA + sub * 16 + g * 4));
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][t], bv[ni][t], acc[mi][ni], 0, 0, 0);
-      }
-    }
-    __syncthreads();  // every wave is done with As / Bs
-    // D[i = 4 g + e][j = r]: i a query of block mi, j a bank row of this wave's block ni.  -0 is stored as +0, so that
-    // which of two equal zeros a list keeps cannot depend on the order they came in
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = acc[mi][ni][e];
-          Sim[(mi * 16 + 4 * g + e) * LDSIM + w * 64 + ni * 16 + r] = v == 0.f ? 0.f : v;
-        }
-    __syncthreads();
+  // -0 arrives as +0, so that which of two equal zeros a list keeps cannot depend on the order they came in
+  walk<true>(a.feats, a.bank, a.P, q0, nq, lo, hi, knn_lds, [=](int64_t, int ncols) {
     for (int qi = 0; qi < Q / 4; ++qi) {  // wave w owns queries 16 w .. 16 w + 15, state included
       const int q = w * (Q / 4) + qi;
       if (q >= nq) break;
       float* list = a.work + ((int64_t)s * a.B + q0 + q) * (int64_t)k;
       float th = st_th[q];
       int cnt = st_cnt[q], mp = st_mp[q];
-      knn_select_row(Sim + q * LDSIM, ncols, list, k, lane, cnt, th, mp);
+      knn_select_row(knn_lds + q * LDSIM, ncols, list, k, lane, cnt, th, mp);
       if (lane == 0) {
         st_th[q] = th;
         st_cnt[q] = cnt;
         st_mp[q] = mp;
       }
     }
-  }
+  });
   __syncthreads();
   // slots no candidate reached (k above the split's rows, NaN similarities, an empty split)
   for (int qi = 0; qi < Q / 4; ++qi) {
@@ -253,31 +175,15 @@ __global__ __launch_bounds__(knn::THREADS) void knn_merge_kernel(const float* wo
 
 }  // namespace
 
-int knn_auto_splits(int B, int64_t N) {
-  int cus = device_cu_count();
-  if (cus <= 0) cus = 256;
-  const int64_t qtiles = ((int64_t)B + knn::Q - 1) / knn::Q;
-  const int64_t tiles = (N + knn::TN - 1) / knn::TN;
-  int64_t want = (2 * (int64_t)cus + qtiles - 1) / qtiles;  // two workgroups fit a CU's LDS
-  if (want > tiles) want = tiles;
-  if (want > MCM_KNN_MAX_SPLITS) want = MCM_KNN_MAX_SPLITS;
-  return want < 1 ? 1 : (int)want;
-}
-
 hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, int P, int k, int S, float* work,
                       float* scores, float* topv, hipStream_t s) {
   if (B < 1 || N < 1 || P < 4 || P % 4 || k < 1 || k > MCM_KNN_MAX_K || S < 1 || S > MCM_KNN_MAX_SPLITS)
     return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)knn_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       knn::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)knn_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            knn::MERGE_LDS_MAX);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
+  static PerDeviceFlag partial_set, merge_set;
+  hipError_t e = bank_sim::lds_limit_once(partial_set, (const void*)knn_partial_kernel, knn::LDS_BYTES);
+  if (e != hipSuccess) return e;
+  e = bank_sim::lds_limit_once(merge_set, (const void*)knn_merge_kernel, knn::MERGE_LDS_MAX);
+  if (e != hipSuccess) return e;
   KnnArgs a;
   a.feats = feats;
   a.bank = bank;
@@ -288,9 +194,9 @@ hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, i
   a.P = P;
   a.k = k;
   a.S = S;
-  const unsigned qtiles = (unsigned)(((int64_t)B + knn::Q - 1) / knn::Q);
-  hipLaunchKernelGGL(knn_partial_kernel, dim3(qtiles, (unsigned)S), dim3(knn::THREADS), knn::LDS_BYTES, s, a);
-  hipError_t e = hipGetLastError();
+  hipLaunchKernelGGL(knn_partial_kernel, dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(knn::THREADS), knn::LDS_BYTES,
+                     s, a);
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
   int npow2 = 1;
   while (npow2 < S * k) npow2 <<= 1;

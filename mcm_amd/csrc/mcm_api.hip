@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "bank_sim.hpp"
 #include "common.hpp"
 
 namespace {
@@ -834,19 +835,34 @@ int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev, int32_t B, co
 }
 
 namespace {
-// the argument rules both k-NN entries share; *S_out = the split count the call runs with
-int knn_check(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int* S_out) {
-  if (B < 1 || N < 1 || k < 1 || k > MCM_KNN_MAX_K || splits < 0 || splits > MCM_KNN_MAX_SPLITS) return MCM_EINVAL;
-  if (h->cfg.proj_dim < 4 || h->cfg.proj_dim % 4) return MCM_EINVAL;
-  *S_out = splits ? splits : knn_auto_splits(B, N);
-  return MCM_OK;
+// The gate of the four entries of the bank-streamed scores (k-NN, NegLabel), for what they share: the handle, B, the width,
+// `splits`, and *S_out = the split count a call over N bank rows runs with.  `own_ok`: the score's own rules.
+bool bank_args_ok(const mcm_handle* h, bool own_ok, int32_t B, int64_t N, int32_t splits, int* S_out) {
+  if (!h || !own_ok || B < 1 || splits < 0 || splits > MCM_KNN_MAX_SPLITS) return false;
+  if (h->cfg.proj_dim < 4 || h->cfg.proj_dim % 4) return false;
+  *S_out = splits ? splits : bank_auto_splits(B, N);
+  return true;
+}
+
+// ... and of the two that launch: what the walk's 16-byte loads and the workspace need (0 = passed)
+int bank_buffers(mcm_handle* h, const float* feats_dev, const float* bank_dev, int64_t work_bytes, int64_t need,
+                 const char* floor_msg) {
+  if (((uintptr_t)feats_dev | (uintptr_t)bank_dev) & 15) return fail(h, MCM_EINVAL, "feats_dev / bank_dev must be 16-byte aligned");
+  return work_bytes < need ? fail(h, MCM_EINVAL, floor_msg) : MCM_OK;
+}
+
+bool knn_ok(int64_t N, int32_t k) { return N >= 1 && k >= 1 && k <= MCM_KNN_MAX_K; }
+int64_t knn_work_bytes(int B, int k, int S) { return (int64_t)S * B * k * (int64_t)sizeof(float); }
+
+bool neglabel_ok(int32_t K, int32_t G, int32_t gs) {
+  return K >= 1 && G >= 1 && G <= MCM_NEG_MAX_GROUPS && gs >= 1 && (int64_t)K + (int64_t)G * gs <= INT32_MAX;
 }
 }  // namespace
 
 int mcm_knn_workspace_bytes(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int64_t* bytes_out) {
   int S = 0;
-  if (!h || !bytes_out || knn_check(h, B, N, k, splits, &S)) return MCM_EINVAL;
-  *bytes_out = (int64_t)S * B * k * (int64_t)sizeof(float);
+  if (!bytes_out || !bank_args_ok(h, knn_ok(N, k), B, N, splits, &S)) return MCM_EINVAL;
+  *bytes_out = knn_work_bytes(B, k, S);
   return MCM_OK;
 }
 
@@ -855,33 +871,21 @@ int mcm_knn_score_features(mcm_handle* h, const float* feats_dev, int32_t B, con
                            void* stream) {
   if (!h) return MCM_EINVAL;
   int S = 0;
-  if (!feats_dev || !bank_dev || !work_dev || !scores_dev || knn_check(h, B, N, k, splits, &S))
+  if (!feats_dev || !bank_dev || !work_dev || !scores_dev || !bank_args_ok(h, knn_ok(N, k), B, N, splits, &S))
     return fail(h, MCM_EINVAL, "bad argument");
-  if (((uintptr_t)feats_dev | (uintptr_t)bank_dev) & 15) return fail(h, MCM_EINVAL, "feats_dev / bank_dev must be 16-byte aligned");
-  if (work_bytes < (int64_t)S * B * k * (int64_t)sizeof(float))
-    return fail(h, MCM_EINVAL, "work_bytes is below mcm_knn_workspace_bytes");
+  if (int rc = bank_buffers(h, feats_dev, bank_dev, work_bytes, knn_work_bytes(B, k, S),
+                            "work_bytes is below mcm_knn_workspace_bytes"))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * (double)N * h->cfg.proj_dim);
   HIP_TRY(h, launch_knn(feats_dev, B, bank_dev, N, h->cfg.proj_dim, k, S, (float*)work_dev, scores_dev, topv_dev, s));
   return MCM_OK;
 }
 
-namespace {
-// the argument rules both NegLabel entries share; *S_out = the split count the call runs with
-int neglabel_check(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits, int* S_out) {
-  if (B < 1 || K < 1 || G < 1 || G > MCM_NEG_MAX_GROUPS || gs < 1 || splits < 0 || splits > MCM_KNN_MAX_SPLITS)
-    return MCM_EINVAL;
-  if ((int64_t)K + (int64_t)G * gs > INT32_MAX) return MCM_EINVAL;
-  if (h->cfg.proj_dim < 4 || h->cfg.proj_dim % 4) return MCM_EINVAL;
-  *S_out = splits ? splits : knn_auto_splits(B, (int64_t)K + (int64_t)G * gs);
-  return MCM_OK;
-}
-}  // namespace
-
 int mcm_neglabel_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits,
                                  int64_t* bytes_out) {
   int S = 0;
-  if (!h || !bytes_out || neglabel_check(h, B, K, G, gs, splits, &S)) return MCM_EINVAL;
+  if (!bytes_out || !bank_args_ok(h, neglabel_ok(K, G, gs), B, (int64_t)K + (int64_t)G * gs, splits, &S)) return MCM_EINVAL;
   *bytes_out = neglabel_work_bytes(B, G, S);
   return MCM_OK;
 }
@@ -891,12 +895,13 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev, int32_t B
                                 float* scores_dev, float* group_dev, void* stream) {
   if (!h) return MCM_EINVAL;
   int S = 0;
-  if (!feats_dev || !bank_dev || !work_dev || !scores_dev || neglabel_check(h, B, K, G, gs, splits, &S))
+  if (!feats_dev || !bank_dev || !work_dev || !scores_dev ||
+      !bank_args_ok(h, neglabel_ok(K, G, gs), B, (int64_t)K + (int64_t)G * gs, splits, &S))
     return fail(h, MCM_EINVAL, "bad argument");
   if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
-  if (((uintptr_t)feats_dev | (uintptr_t)bank_dev) & 15) return fail(h, MCM_EINVAL, "feats_dev / bank_dev must be 16-byte aligned");
-  if (work_bytes < neglabel_work_bytes(B, G, S))
-    return fail(h, MCM_EINVAL, "work_bytes is below mcm_neglabel_workspace_bytes");
+  if (int rc = bank_buffers(h, feats_dev, bank_dev, work_bytes, neglabel_work_bytes(B, G, S),
+                            "work_bytes is below mcm_neglabel_workspace_bytes"))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * ((double)K + (double)G * gs) * h->cfg.proj_dim);
   HIP_TRY(h, launch_neglabel(feats_dev, B, bank_dev, K, G, gs, h->cfg.proj_dim, T, S, work_dev, scores_dev, group_dev, s));

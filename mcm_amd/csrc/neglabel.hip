@@ -1,13 +1,12 @@
 // neglabel.hip — the NegLabel score (include/mcm.h mcm_neglabel_score_features): the share of a query's
 // softmax mass that falls on the ID rows of a bank of K ID prompts and G groups of gs negative prompts, taken against
 // every group alone and averaged, without the [B, N] matrix ever existing in HBM.  The bank's rows fall into G + 1
-// contiguous *ranges*: range 0 = rows [0, K), range 1 + g = rows [K + g gs, K + (g + 1) gs).  Two launches in stream order,
-// on the plan of knn.hip:
-//   neg_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows in tiles of 256: the
-//                       64 x 256 similarities are accumulated by the exact-fp32 MFMA (staging and tile as in knn.hip) and
-//                       written to LDS.  A tile is cut into segments (a range intersected with the tile); a wave per query
-//                       folds every segment into the open online-softmax pair (max, sum exp((s - max) / T)) of its range,
-//                       the sum in fp64.  The pair is written to work[split, query, range] when its range or the split ends.
+// contiguous *ranges*: range 0 = rows [0, K), range 1 + g = rows [K + g gs, K + (g + 1) gs).  Two launches in stream order:
+//   neg_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows (bank_sim.hpp: the
+//                       64 x 256 exact-fp32 similarities of a tile in LDS, the s[b, n] that knn.hip sees).  A tile is cut
+//                       into segments (a range intersected with the tile); a wave per query folds every segment into
+//                       the open online-softmax pair (max, sum exp((s - max) / T)) of its range, the sum in fp64.  The
+//                       pair is written to work[split, query, range] when its range or the split ends.
 //   neg_combine_kernel  one workgroup per query: per range the partial pairs of the splits that hold rows of it, in split
 //                       order, give its log-sum-exp in fp64; S[g] = 1 / (1 + exp(LN[g] - LI)); the mean is a fixed tree.
 // Which (split, range) slots were written follows from K, gs and the split length alone, and the second launch reads
@@ -16,23 +15,15 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "bank_sim.hpp"
 
 namespace {
 
 namespace neg {
-constexpr int Q = 64;             // queries of a workgroup
-constexpr int TN = 256;           // bank rows of a tile
-constexpr int KC = 32;            // feature columns of a staged chunk
-constexpr int LDA = KC + 4;       // LDS row stride of a staged operand (floats; rows stay 16-byte aligned)
-constexpr int LDSIM = TN + 4;     // LDS row stride of the similarity tile
-constexpr int THREADS = 256;
-constexpr int STAGE_FLOATS = (Q + TN) * LDA;
-constexpr int SIM_FLOATS = Q * LDSIM;  // the similarity tile lies over the staging buffers (they are dead by then)
+using namespace bank_sim;
 // behind the tile: the open pair of every query, sum [Q] fp64 then max [Q] fp32
-constexpr int LDS_BYTES = SIM_FLOATS * (int)sizeof(float) + Q * (int)(sizeof(double) + sizeof(float));
-static_assert(STAGE_FLOATS <= SIM_FLOATS, "the staging buffers must fit under the similarity tile");
-static_assert(SIM_FLOATS * sizeof(float) % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
+constexpr int LDS_BYTES = TILE_BYTES + Q * (int)(sizeof(double) + sizeof(float));
+static_assert(TILE_BYTES % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
 }  // namespace neg
 
 struct NegArgs {
@@ -60,22 +51,15 @@ __device__ __forceinline__ double neg_wave_sum(double x) {
 __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
   using namespace neg;
   extern __shared__ __attribute__((aligned(16))) float neg_lds[];
-  float* As = neg_lds;             // [Q][LDA]
-  float* Bs = neg_lds + Q * LDA;   // [TN][LDA]
-  float* Sim = neg_lds;            // [Q][LDSIM], over As / Bs
   double* st_sum = (double*)(neg_lds + SIM_FLOATS);
   float* st_max = (float*)(st_sum + Q);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int g = lane >> 4, r = lane & 15;
   const int q0 = blockIdx.x * Q;
   const int nq = a.B - q0 < Q ? a.B - q0 : Q;
   const int s = blockIdx.y;
-  const int64_t lo64 = (int64_t)s * a.per;
-  const int lo = lo64 < a.N ? (int)lo64 : a.N;
-  const int hi = (int64_t)lo + a.per < a.N ? lo + a.per : a.N;
-  const int P = a.P;
-  const int nchunks = (P + KC - 1) / KC;
+  int64_t lo, hi;
+  split_bounds(s, a.per, a.N, lo, hi);
 
   if (tid < Q) {
     st_sum[tid] = 0.0;
@@ -83,75 +67,13 @@ __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
   }
   __syncthreads();
 
-  const int ld_row = tid >> 3, ld_c4 = (tid & 7) * 4;  // a thread's share of a chunk: rows ld_row + 32 i, 4 columns
-  for (int n0 = lo; n0 < hi; n0 += TN) {
-    const int ncols = hi - n0 < TN ? hi - n0 : TN;
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    float4 ra[2], rb[8];
-    auto gload = [&](int kc) {
-      const int col = kc * KC + ld_c4;
-      const bool cok = col < P;  // P % 4 == 0: four columns are in or out together
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = ld_row + 32 * i;
-        ra[i] = (cok && row < nq) ? *(const float4*)(a.feats + (int64_t)(q0 + row) * P + col) : float4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int row = ld_row + 32 * i;
-        rb[i] = (cok && row < ncols) ? *(const float4*)(a.bank + ((int64_t)n0 + row) * (int64_t)P + col)
-                                     : float4{0.f, 0.f, 0.f, 0.f};
-      }
-    };
-    gload(0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-      __syncthreads();  // the chunk (or the similarity tile) under these bytes has been read
-#pragma unroll
-      for (int i = 0; i < 2; ++i) *(float4*)(As + (ld_row + 32 * i) * LDA + ld_c4) = ra[i];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) *(float4*)(Bs + (ld_row + 32 * i) * LDA + ld_c4) = rb[i];
-      __syncthreads();
-      if (kc + 1 < nchunks) gload(kc + 1);  // in flight under the MFMAs
-#pragma unroll
-      for (int sub = 0; sub < KC / 16; ++sub) {
-        // lane (g, r) takes columns 16 sub + 4 g .. + 3 of its rows as one 16-byte read; MFMA t of the four then
-        // multiplies column 16 sub + 4 g + t of both operands (knn.hip: the same accumulation, so the same s[b, n])
-        f32x4_t av[4], bv[4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-          av[mi] = __builtin_bit_cast(f32x4_t, *(const float4*)(As + (mi * 16 + r) * LDA + sub * 16 + g * 4));
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          bv[ni] = __builtin_bit_cast(f32x4_t, *(const float4*)(Bs + (w * 64 + ni * 16 + r) * LDA + sub * 16 + g * 4));
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mi][t], bv[ni][t], acc[mi][ni], 0, 0, 0);
-      }
-    }
-    __syncthreads();  // every wave is done with As / Bs
-    // D[i = 4 g + e][j = r]: i a query of block mi, j a bank row of this wave's block ni
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) Sim[(mi * 16 + 4 * g + e) * LDSIM + w * 64 + ni * 16 + r] = acc[mi][ni][e];
-    __syncthreads();
-
-    const int tile_end = n0 + ncols;
+  // either zero gives the same bits in everything below: the tile is taken as the MFMA left it
+  walk<false>(a.feats, a.bank, a.P, q0, nq, lo, hi, neg_lds, [=](int64_t tile0, int ncols) {
+    const int n0 = (int)tile0, tile_end = n0 + ncols;  // N <= INT_MAX
     for (int qi = 0; qi < Q / 4; ++qi) {  // wave w owns queries 16 w .. 16 w + 15, their open pairs included
       const int q = w * (Q / 4) + qi;
       if (q >= nq) break;
-      const float* row = Sim + q * LDSIM;
+      const float* row = neg_lds + q * LDSIM;
       float m = st_max[q];
       double sum = st_sum[q];
       int c = 0;
@@ -181,8 +103,7 @@ __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
         st_sum[q] = sum;
       }
     }
-    if (n0 > INT_MAX - TN) break;  // this was the last tile (hi <= INT_MAX), and n0 += TN would overflow
-  }
+  });
 }
 
 struct NegCombineArgs {
@@ -241,12 +162,8 @@ hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, 
       !(T > 0.f) || !isfinite(T) || (int64_t)K + (int64_t)G * gs > INT_MAX)
     return hipErrorInvalidValue;
   static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)neg_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       neg::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
+  hipError_t e = bank_sim::lds_limit_once(attr_set, (const void*)neg_partial_kernel, neg::LDS_BYTES);
+  if (e != hipSuccess) return e;
   const int N = K + G * gs;
   NegArgs a;
   a.feats = feats;
@@ -260,9 +177,9 @@ hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, 
   a.K = K;
   a.G = G;
   a.gs = gs;
-  const unsigned qtiles = (unsigned)(((int64_t)B + neg::Q - 1) / neg::Q);
-  hipLaunchKernelGGL(neg_partial_kernel, dim3(qtiles, (unsigned)S), dim3(neg::THREADS), neg::LDS_BYTES, s, a);
-  hipError_t e = hipGetLastError();
+  hipLaunchKernelGGL(neg_partial_kernel, dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(neg::THREADS), neg::LDS_BYTES,
+                     s, a);
+  e = hipGetLastError();
   if (e != hipSuccess) return e;
   NegCombineArgs c;
   c.work = (const float2*)work;

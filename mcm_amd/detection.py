@@ -263,6 +263,50 @@ def shard_loader(loader, lo: int, hi: int):
     return DataLoader(Subset(ds, range(lo, hi)), **kw)
 
 
+def _shard_batches(loader, n, what):
+    """This rank's (images, labels) batches of samples [0, n) of `loader.dataset`, in order: all of them for one rank, the
+    rank's `shard_range` under world_size > 1, where a loader `shard_loader` cannot split by index is refused (`what`: the
+    --score named in the refusal, raised by this call and not by the first batch).  The last batch is cut to the range's
+    end, images and labels alike."""
+    rank, ws = mdist.world()
+    batches, lo, hi = loader, 0, n
+    if ws > 1:
+        lo, hi = mdist.shard_range(n, rank, ws)
+        batches = shard_loader(loader, lo, hi)
+        if batches is None:
+            raise TypeError(f"--score {what} under world_size > 1 needs a loader that can be sharded by index")
+
+    def walk():
+        seen = 0
+        for images, labels in (batches if hi > lo else ()):
+            if seen >= hi - lo:
+                break
+            if images.shape[0] > hi - lo - seen:
+                images, labels = images[: hi - lo - seen], labels[: hi - lo - seen]
+            yield images, labels
+            seen += images.shape[0]
+
+    return walk()
+
+
+def _feature_home(args, net):
+    """(device, width) of the feature rows of `net`, for the empty shard of a rank without samples."""
+    P = getattr(getattr(net, "geo", None), "proj_dim", None) or getattr(args, "feat_dim", 0)
+    return getattr(net, "device", None) or "cpu", int(P)
+
+
+def _gather_shards(parts, n_total, device, width=None):
+    """What `_shard_batches` produced on every rank, in dataset order, on every rank: this rank's `parts` joined (no part: an
+    empty fp32 tensor on `device`, [0] scores or [0, width] rows), all-gathered where a process group exists, cut to n_total."""
+    import torch
+
+    shape = (0,) if width is None else (0, width)
+    local = torch.cat(parts) if parts else torch.empty(shape, dtype=torch.float32, device=device)
+    if mdist.group_active():
+        local = (mdist.all_gather_scores if width is None else mdist.all_gather_rows)(local, n_total)
+    return local.detach()[:n_total]
+
+
 def get_mean_prec(args, net, train_loader):
     """Mahalanobis fit: (classwise_mean [n_cls, feat_dim], precision [feat_dim, feat_dim]), with the
     results and side effects of reference utils/detection_util.py:146-174.  Two behaviours of the
@@ -426,28 +470,14 @@ def get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_
     total_len = len(test_loader.dataset)
     # the samples the reference scores: everything for the ID set, whole batches only for an OOD set
     n_scored = total_len if in_dist else min(total_len, (total_len // args.batch_size) * args.batch_size)
-    rank, ws = mdist.world()
-    batches, lo, hi = test_loader, 0, n_scored
-    if ws > 1:  # image-sharded like get_ood_scores_clip: a contiguous index range per rank, all-gathered at the end
-        lo, hi = mdist.shard_range(n_scored, rank, ws)
-        batches = shard_loader(test_loader, lo, hi)
-        if batches is None:
-            raise TypeError("--score maha under world_size > 1 needs a loader that can be sharded by index")
-    out, seen = [], 0
-    with torch.no_grad():
-        for images, _labels in batches:
-            if seen >= hi - lo:
-                break
-            images = images[: hi - lo - seen]
+    out = []
+    with torch.no_grad():  # image-sharded like get_ood_scores_clip: a contiguous index range per rank, all-gathered at the end
+        for images, _labels in _shard_batches(test_loader, n_scored, "maha"):
             features = net.get_image_features(pixel_values=images).float()
             if args.normalize:
                 features = features / features.norm(dim=-1, keepdim=True)
             out.append(net.maha_scores(features, state))
-            seen += images.shape[0]
-    res = torch.cat(out) if out else torch.empty(0, device=state["prec"].device)
-    if mdist.group_active():
-        res = mdist.all_gather_scores(res, n_scored)
-    return res.cpu().numpy().astype(np.float32)
+    return _gather_shards(out, n_scored, state["prec"].device).cpu().numpy().astype(np.float32)
 
 
 def knn_auto_k(n_bank):
@@ -472,28 +502,10 @@ def get_knn_bank(args, net, train_loader):
 
     if not hasattr(net, "knn_scores"):
         raise TypeError("get_knn_bank needs a net with knn_scores (a NativeCLIP); there is no eager fallback")
-    rank, ws = mdist.world()
     n_total = len(train_loader.dataset)
-    batches, lo, hi = train_loader, 0, n_total
-    if ws > 1:
-        lo, hi = mdist.shard_range(n_total, rank, ws)
-        batches = shard_loader(train_loader, lo, hi)
-        if batches is None:
-            raise TypeError("--score knn under world_size > 1 needs a loader that can be sharded by index")
-    parts, seen = [], 0
     with torch.no_grad():
-        for images, _labels in (batches if hi > lo else ()):
-            if seen >= hi - lo:
-                break
-            f = _unit_image_features(net, images[: hi - lo - seen])
-            parts.append(f)
-            seen += f.shape[0]
-        P = getattr(getattr(net, "geo", None), "proj_dim", None) or getattr(args, "feat_dim", 0)
-        dev = getattr(net, "device", None) or "cpu"
-        local = torch.cat(parts) if parts else torch.empty((0, int(P)), dtype=torch.float32, device=dev)
-        if mdist.group_active():
-            local = mdist.all_gather_rows(local, n_total)
-    return local.detach()[:n_total].contiguous()
+        parts = [_unit_image_features(net, images) for images, _labels in _shard_batches(train_loader, n_total, "knn")]
+        return _gather_shards(parts, n_total, *_feature_home(args, net)).contiguous()
 
 
 def get_knn_score(args, net, loader, bank, k):
@@ -506,26 +518,11 @@ def get_knn_score(args, net, loader, bank, k):
     k = int(k)
     if not 1 <= k <= len(bank):
         raise ValueError(f"--score knn: k = {k} needs 1 <= k <= the bank's {len(bank)} rows")
-    rank, ws = mdist.world()
     n_total = len(loader.dataset)
-    batches, lo, hi = loader, 0, n_total
-    if ws > 1:
-        lo, hi = mdist.shard_range(n_total, rank, ws)
-        batches = shard_loader(loader, lo, hi)
-        if batches is None:
-            raise TypeError("--score knn under world_size > 1 needs a loader that can be sharded by index")
-    out, seen = [], 0
     with torch.no_grad():
-        for images, _labels in (batches if hi > lo else ()):
-            if seen >= hi - lo:
-                break
-            f = _unit_image_features(net, images[: hi - lo - seen])
-            out.append(net.knn_scores(f, bank, k))
-            seen += f.shape[0]
-    res = torch.cat(out) if out else torch.empty(0, dtype=torch.float32, device=bank.device)
-    if mdist.group_active():
-        res = mdist.all_gather_scores(res, n_total)
-    return res.detach().cpu().numpy().astype(np.float32)[:n_total]
+        out = [net.knn_scores(_unit_image_features(net, images), bank, k)
+               for images, _labels in _shard_batches(loader, n_total, "knn")]
+    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
 
 
 NEG_MAX_GROUPS = 1024  # MCM_NEG_MAX_GROUPS of include/mcm.h
@@ -562,13 +559,7 @@ def _candidate_features(args, net, cands):
         else:
             tok = _tokenizer(args, net)([PROMPT.format(c=c) for c in cands], padding=True, return_tensors="pt")
             local = _unit_text_features(net, {"input_ids": tok["input_ids"][lo:hi], "attention_mask": tok["attention_mask"][lo:hi]})
-        if local is None:
-            P = getattr(getattr(net, "geo", None), "proj_dim", None) or getattr(args, "feat_dim", 0)
-            local = torch.empty((0, int(P)), dtype=torch.float32, device=getattr(net, "device", None) or "cpu")
-        local = local.float()
-        if mdist.group_active():
-            local = mdist.all_gather_rows(local.contiguous(), C)
-    return local.detach()[:C].contiguous()
+        return _gather_shards([] if local is None else [local.float().contiguous()], C, *_feature_home(args, net)).contiguous()
 
 
 def _mine(args, net, id_names, words):
@@ -647,26 +638,11 @@ def get_neglabel_score(args, net, loader, bank_info):
         raise TypeError("get_neglabel_score needs a net with neglabel_scores (a NativeCLIP); there is no eager fallback")
     bank, K, G, gs = bank_info["bank"], int(bank_info["K"]), int(bank_info["G"]), int(bank_info["gs"])
     T = float(getattr(args, "neg_T", 0.01))
-    rank, ws = mdist.world()
     n_total = len(loader.dataset)
-    batches, lo, hi = loader, 0, n_total
-    if ws > 1:
-        lo, hi = mdist.shard_range(n_total, rank, ws)
-        batches = shard_loader(loader, lo, hi)
-        if batches is None:
-            raise TypeError("--score neglabel under world_size > 1 needs a loader that can be sharded by index")
-    out, seen = [], 0
     with torch.no_grad():
-        for images, _labels in (batches if hi > lo else ()):
-            if seen >= hi - lo:
-                break
-            f = _unit_image_features(net, images[: hi - lo - seen])
-            out.append(net.neglabel_scores(f, bank, K, G, gs, T=T))
-            seen += f.shape[0]
-    res = torch.cat(out) if out else torch.empty(0, dtype=torch.float32, device=bank.device)
-    if mdist.group_active():
-        res = mdist.all_gather_scores(res, n_total)
-    return res.detach().cpu().numpy().astype(np.float32)[:n_total]
+        out = [net.neglabel_scores(_unit_image_features(net, images), bank, K, G, gs, T=T)
+               for images, _labels in _shard_batches(loader, n_total, "neglabel")]
+    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
 
 
 def _gather_batch_shards(local, n_total, ws):

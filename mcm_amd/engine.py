@@ -370,25 +370,44 @@ class NativeCLIP:
         go through in blocks of at most 4096 rows."""
         import torch
 
-        f = features.to(device=self.device, dtype=torch.float32).contiguous()
-        bk = bank.to(device=self.device, dtype=torch.float32).contiguous()
-        P, k, splits = self.geo.proj_dim, int(k), int(splits)
-        if f.dim() != 2 or f.shape[1] != P or bk.dim() != 2 or bk.shape[1] != P:
-            raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
+        f, bk = self._bank_operands(features, bank)
+        k, splits = int(k), int(splits)
         B, N = int(f.shape[0]), int(bk.shape[0])
         scores = torch.empty(B, device=self.device, dtype=torch.float32)
         topv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32) if return_values else None
-        for s in range(0, max(B, 1), 4096):
-            n = min(4096, B - s)
-            need = ctypes.c_int64(0)
-            self._check_knn(self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, ctypes.byref(need)), n, N, k, splits)
-            work = getattr(self, "_knn_work", None)
-            if work is None or work.numel() * 4 < need.value:
-                work = self._knn_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+        for s, n, work in self._bank_blocks(B, getattr(self, "_knn_work", None), lambda n, need: self._check_knn(
+                self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, need), n, N, k, splits)):
+            self._knn_work = work
             self._check(self._lib.mcm_knn_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), N, k, splits, work.data_ptr(), work.numel() * 4,
                 scores[s:s + n].data_ptr(), topv[s:s + n].data_ptr() if return_values else None, _stream_ptr()))
         return (scores, topv) if return_values else scores
+
+    def _bank_operands(self, features, bank):
+        """(features, bank) as contiguous fp32 device tensors, both [*, proj_dim] (the operands of a bank-streamed score)."""
+        import torch
+
+        f = features.to(device=self.device, dtype=torch.float32).contiguous()
+        bk = bank.to(device=self.device, dtype=torch.float32).contiguous()
+        P = self.geo.proj_dim
+        if f.dim() != 2 or f.shape[1] != P or bk.dim() != 2 or bk.shape[1] != P:
+            raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
+        return f, bk
+
+    def _bank_blocks(self, B, work, workspace_bytes):
+        """The B queries of a bank-streamed score in blocks of at most 4096 rows, as (start, n, work): workspace_bytes(n,
+        byref(int64)) asks the library what a block of n needs (and raises where it refuses); `work` is the caller's buffer
+        (or None), replaced by a larger one where it is too small.  The caller keeps what it is handed: one buffer per
+        score, since two scores may be in flight on two streams."""
+        import torch
+
+        for s in range(0, max(B, 1), 4096):
+            n = min(4096, B - s)
+            need = ctypes.c_int64(0)
+            workspace_bytes(n, ctypes.byref(need))
+            if work is None or work.numel() * 4 < need.value:
+                work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+            yield s, n, work
 
     def _check_knn(self, rc, B, N, k, splits):
         if rc:
@@ -405,24 +424,16 @@ class NativeCLIP:
         demand; queries go through in blocks of at most 4096 rows."""
         import torch
 
-        f = features.to(device=self.device, dtype=torch.float32).contiguous()
-        bk = bank.to(device=self.device, dtype=torch.float32).contiguous()
-        P, K, G, gs, splits, T = self.geo.proj_dim, int(n_id), int(groups), int(group_size), int(splits), float(T)
-        if f.dim() != 2 or f.shape[1] != P or bk.dim() != 2 or bk.shape[1] != P:
-            raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
+        f, bk = self._bank_operands(features, bank)
+        K, G, gs, splits, T = int(n_id), int(groups), int(group_size), int(splits), float(T)
         if K < 1 or G < 1 or gs < 1 or bk.shape[0] != K + G * gs:
             raise ValueError(f"neglabel_scores: the bank has {bk.shape[0]} rows, n_id + groups * group_size = {K} + {G} * {gs}")
         B = int(f.shape[0])
         scores = torch.empty(B, device=self.device, dtype=torch.float32)
         grp = torch.empty((B, G), device=self.device, dtype=torch.float32) if return_groups else None
-        for s in range(0, max(B, 1), 4096):
-            n = min(4096, B - s)
-            need = ctypes.c_int64(0)
-            self._check_neglabel(self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, ctypes.byref(need)),
-                                 n, K, G, gs, T, splits)
-            work = getattr(self, "_neg_work", None)
-            if work is None or work.numel() * 4 < need.value:
-                work = self._neg_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+        for s, n, work in self._bank_blocks(B, getattr(self, "_neg_work", None), lambda n, need: self._check_neglabel(
+                self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, need), n, K, G, gs, T, splits)):
+            self._neg_work = work
             self._check_neglabel(self._lib.mcm_neglabel_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, G, gs, T, splits, work.data_ptr(), work.numel() * 4,
                 scores[s:s + n].data_ptr(), grp[s:s + n].data_ptr() if return_groups else None, _stream_ptr()),

@@ -1,0 +1,36 @@
+"""Record tests/golden/bank_walk_frozen.npz: the bits of the k-NN and NegLabel scores at the cases of
+tests/test_gpu_bank_walk_frozen.py, as the library built in this tree computes them on an MI355X, with the ROCm version and the
+commit they were made at.
+
+  python tests/golden/make_bank_walk_frozen.py --commit HASH [--out FILE]
+
+The fixture in git was recorded at the commit before knn.hip and neglabel.hip took their walk from bank_sim.hpp.  Run this only
+at a commit whose bits are meant to become the yardstick, never to make a failing test pass."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(HERE, "bank_walk_frozen.npz"))
+    ap.add_argument("--commit", required=True, help="the commit this tree is a checkout of (recorded in the fixture)")
+    a = ap.parse_args()
+    import torch
+
+    from tests.test_gpu_bank_walk_frozen import frozen_outputs
+
+    out = frozen_outputs()
+    np.savez_compressed(a.out, rocm=np.array(str(torch.version.hip)), commit=np.array(a.commit), **out)
+    print(f"{a.out}: {len(out)} arrays, {os.path.getsize(a.out)} bytes, ROCm {torch.version.hip}, commit {a.commit}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
