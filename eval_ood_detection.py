@@ -54,7 +54,7 @@ def process_args(argv=None):
                             "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
-                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel"], help="score options")
+                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel", "GL-MCM"], help="score options")
     # Mahalanobis baseline (--score maha), reference eval_ood_detection.py:38-44
     p.add_argument("--feat_dim", type=int, default=512)
     p.add_argument("--normalize", type=bool, default=False)
@@ -134,7 +134,20 @@ def process_args(argv=None):
     p.add_argument("--neg-groups", default=100, type=int, metavar="G",
                    help="--score neglabel: the kept words are cut into min(G, M) consecutive groups of floor(M / G); 1..1024")
     p.add_argument("--neg-T", default=0.01, type=float, help="--score neglabel: the softmax temperature (--T is ignored there)")
+    p.add_argument("--gl-lambda", default=1.0, type=float, metavar="L",
+                   help="--score GL-MCM (Miyai et al.: MCM plus a local term, the best softmax match of any single image patch's "
+                        "value-path feature): the score is -(S_G + L S_L); default 1")
     args = p.parse_args(argv)
+    if args.score == "GL-MCM":
+        if not np.isfinite(args.gl_lambda):
+            p.error("--gl-lambda must be finite")
+        if args.dtype == "fp16x2":
+            p.error("--score GL-MCM has no split-activation arm: --dtype fp16x2 is not available with it")
+        if args.refine_threshold in ("on", "exact"):
+            p.error("--refine-threshold on / exact is not available with --score GL-MCM (no re-scoring arm for the local term)")
+        if args.predict:
+            p.error("--predict is not available with --score GL-MCM")
+        args.refine_threshold = "off"  # auto resolves to off
     if args.score == "neglabel":
         if not args.neg_words:
             p.error("--score neglabel needs --neg-words FILE (one candidate word per line)")
@@ -293,7 +306,8 @@ def main(argv=None):
     # images, for which half the batch costs nothing extra; otherwise the workspace is not allocated at all
     # the training-set baselines (no prompt bank) and neglabel (a bank of its own): scores come back as host arrays, and
     # there is no threshold refinement
-    no_bank = args.score in ("maha", "knn", "neglabel")
+    # (GL-MCM uses the prompt bank, but like them has no re-scoring arm and hands back host arrays)
+    no_bank = args.score in ("maha", "knn", "neglabel", "GL-MCM")
     will_refine = args.refine_threshold != "off" and not no_bank
     x2_batch = 0 if args.dtype == "fp16x2" else (max(1, args.batch_size // 2) if (args.dtype == "fp16" and will_refine) else -1)
     net = build_model(args.CLIP_ckpt, weights=args.weights, device=dev, precision=args.dtype,
@@ -381,6 +395,11 @@ def main(argv=None):
                   f"M = {neg_bank['M']} kept, G = {neg_bank['G']} groups of gs = {neg_bank['gs']}; kept d from "
                   f"{float(neg_bank['d'].min()):.6f} to {float(neg_bank['d'].max()):.6f} (quantile {args.neg_quantile})")
         in_score = get_neglabel_score(args, net, test_loader, neg_bank)
+    elif args.score == "GL-MCM":
+        from mcm_amd.detection import get_glmcm_scores
+
+        log.debug(f"--score GL-MCM: -(S_G + {args.gl_lambda} S_L) at T = {args.T}, {net.local_rows} patch rows per image")
+        in_score = get_glmcm_scores(args, net, test_loader, test_labels)
     else:
         in_score = _score_set(args, net, test_loader, test_labels, "id", log, rank, on_dev, in_dist=True)
         _note_pillow_files(net, sources, "id", log)
@@ -426,6 +445,8 @@ def main(argv=None):
             out_score = get_knn_score(args, net, ood_loader, knn_bank, knn_k)
         elif args.score == "neglabel":
             out_score = get_neglabel_score(args, net, ood_loader, neg_bank)
+        elif args.score == "GL-MCM":
+            out_score = get_glmcm_scores(args, net, ood_loader, test_labels)
         else:
             out_score = _score_set(args, net, ood_loader, test_labels, out_dataset, log, rank, on_dev)
             _note_pillow_files(net, sources, out_dataset, log)

@@ -43,7 +43,9 @@ extern "C" {
                           * existing entry changed — a caller built against the earlier ABI 5 header runs unchanged
                           * (still 5) mcm_maha_fit_accumulate: an added symbol, on the same terms
                           * (still 5) mcm_knn_workspace_bytes / mcm_knn_score_features: two added symbols, on the same terms
-                          * (still 5) mcm_neglabel_workspace_bytes / mcm_neglabel_score_features: two added symbols, on the same terms */
+                          * (still 5) mcm_neglabel_workspace_bytes / mcm_neglabel_score_features: two added symbols, on the same terms
+                          * (still 5) mcm_local_workspace_bytes / mcm_local_score_features / mcm_encode_image_local /
+                          * mcm_score_glmcm: four added symbols, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -437,6 +439,58 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev /* [B, pro
                                 const float* bank_dev /* [K + G gs, proj_dim] */, int32_t K, int32_t G, int32_t gs,
                                 float T, int32_t splits, void* work_dev, int64_t work_bytes,
                                 float* scores_dev /* [B] */, float* group_dev /* [B, G] or NULL */, void* stream);
+
+/* ---- GL-MCM: a patch-level local score next to MCM (--score GL-MCM; Miyai et al.) ---------------------
+ * score = -(S_G + lambda S_L): S_G the MCM term of the global (CLS) feature, S_L the best concept match of any single
+ * image patch (added under ABI 5: four symbols only).  The definition is taken from the paper (MaskCLIP's value path);
+ * DESIGN.md 4.14.  P = the handle's proj_dim, R = patch tokens per image, everything row-major.
+ *
+ * The local score on features:
+ *   s[b, i, k]      = the fp32 dot product of local_dev[b, i] and text_dev[k] as mcm_knn_score_features defines it (the
+ *                     exact-fp32 MFMA: one rounding per product, operands never narrowed);
+ *   patch[b, i]     = max_k softmax_k(s[b, i, :] / T) = 1 / sum_k exp((s[b, i, k] - max_k s[b, i, k]) / T), the sum carried
+ *                     in fp64 across the bank's 256-row tiles as an online-softmax pair, the result rounded to fp32;
+ *   local_scores[b] = -max_i patch[b, i]; larger = more OOD, the sign every stored score here has.
+ * A NaN anywhere in an image's R x K similarities makes that image's score NaN, and patch NaN for the rows that hold it;
+ * other images are unaffected.  The [B R, K] similarities exist in registers and LDS only.  Two launches: one over the
+ * B R rows in tiles of 64 that writes the row values to work_dev (B R floats; and to patch_dev when given), one workgroup
+ * per image for the maximum.  work_dev needs no initialisation.  The outputs are a pure function of (local_dev, text_dev, T):
+ * the same bits on every run, for every cut of the images into calls and for every image position (no atomics, no
+ * workgroup waits for another).  Asynchronous on `stream`, no allocation, no host synchronisation; timed under
+ * MCM_KC_SCORE (2 B R K P flop).
+ * Refusals (nothing is launched): MCM_EINVAL for a NULL h / local_dev / text_dev / work_dev / local_scores_dev / bytes_out,
+ * B, R or K < 1, B R above INT32_MAX, T <= 0 or not finite, proj_dim % 4 != 0, local_dev / text_dev not 16-byte aligned
+ * (an output not 4-byte aligned), or work_bytes below mcm_local_workspace_bytes.  patch_dev may be NULL. */
+int mcm_local_workspace_bytes(const mcm_handle* h, int32_t B, int32_t R, int32_t K, int64_t* bytes_out);
+int mcm_local_score_features(mcm_handle* h, const float* local_dev /* [B, R, proj_dim] */, int32_t B, int32_t R,
+                             const float* text_dev /* [K, proj_dim] */, int32_t K, float T, void* work_dev,
+                             int64_t work_bytes, float* local_scores_dev /* [B] = -S_L */,
+                             float* patch_dev /* [B, R] or NULL */, void* stream);
+/* The local features from the vision tower.  h_i = the fp32 residual-stream row of token i entering the LAST encoder layer:
+ *   v_i = W_v layer_norm1(h_i) + b_v     the V block the unchanged forward leaves in its workspace
+ *   o_i = W_o v_i + b_o                  the layer's out_proj: no attention mixing, no residual, no MLP
+ *   y_i = W_proj post_layernorm(o_i)     l_i = y_i / |y_i|
+ * for the R = (image_size / patch_size)^2 patch tokens i = 1 .. R of every image (token 0, CLS, is not a local row).  A
+ * variant that re-attaches the residual and the MLP is not implemented.
+ * mcm_encode_image_local runs the forward of mcm_encode_image_ex(normalize = 1) — the same launches, global_dev the same
+ * bits — and behind it the local pass: out_proj and the projection as GEMMs over all B (R + 1) rows in the handle's operand
+ * mode (single or split weights; visual_projection.weight in that form is built by mcm_finalize_weights), post_layernorm,
+ * and one launch that L2-normalises and compacts the rows into local_dev.  Every intermediate lives in workspace the
+ * forward is done with.  No entry other than the two below launches any of it.
+ * mcm_score_glmcm: the same, the local rows kept in the handle's workspace; global_scores[b] = -S_G are the bits of
+ * mcm_score (MCM_SCORE_MCM) for the same pixels, local_scores / patch the bits of mcm_local_score_features on
+ * mcm_encode_image_local's rows, scores[b] = (float)((double) global_scores[b] + (double) lambda (double) local_scores[b]).
+ * There is no split-activation (x2) form of either.  Asynchronous on `stream`, no allocation.
+ * Refusals (nothing is launched): those of mcm_encode_image_ex; MCM_EINVAL for a NULL local_dev / text_dev / scores_dev, a
+ * local_dev or text_dev not 16-byte aligned, K < 1, T <= 0 or not finite, lambda not finite, proj_dim % 16 != 0 or
+ * proj_dim > v_width (the workspace the local pass borrows), a tower without patch tokens. */
+int mcm_encode_image_local(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B,
+                           float* global_dev /* [B, proj_dim], unit-norm */,
+                           float* local_dev /* [B, R, proj_dim], unit-norm */, void* stream);
+int mcm_score_glmcm(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, const float* text_dev /* [K, proj_dim] */,
+                    int32_t K, float T, float lambda, float* scores_dev /* [B] */,
+                    float* global_scores_dev /* [B] or NULL: -S_G */, float* local_scores_dev /* [B] or NULL: -S_L */,
+                    float* patch_dev /* [B, R] or NULL */, void* stream);
 
 /* ---- CLIP byte-level BPE tokenizer, host side --------------------------------
  * Replaces CLIPTokenizer.from_pretrained(args.ckpt) + tokenizer(list[str], padding=True,

@@ -436,6 +436,17 @@ int64_t neglabel_work_bytes(int B, int G, int S);
 hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, int G, int gs, int P, float T, int S,
                            void* work, float* scores, float* group, hipStream_t s);
 
+// glmcm.hip: the local term of GL-MCM over patch rows [B, R, P] against bank [K, P]: patch [B, R] (or nullptr) = the
+// largest softmax probability of every row at temperature T, scores [B] = -max over an image's rows (NaN if a row's is).
+// work holds local_work_bytes(B, R): the row values.
+int64_t local_work_bytes(int B, int R);
+hipError_t launch_local_score(const float* rows, int B, int R, const float* bank, int K, int P, float T, void* work,
+                              float* scores, float* patch, hipStream_t s);
+// projected token rows y [B ntok, P] -> out [B, ntok - 1, P]: token 0 of every image dropped, rows L2-normalised
+hipError_t launch_local_compact(const float* y, float* out, int B, int ntok, int P, hipStream_t s);
+// out[b] = (float)((double) g[b] + (double) lambda * (double) l[b]): the GL-MCM score from its two stored parts
+hipError_t launch_local_combine(const float* g, const float* l, float lambda, float* out, int B, hipStream_t s);
+
 hipError_t launch_score(const float* img, int B, const float* text, int K, int P, float T,
                         int kind, float* scores, hipStream_t s);
 // the top-k form of the same tail (score_kernel<true>): idx [B,topk] int32, prob [B,topk] fp32 or nullptr;

@@ -60,6 +60,7 @@ struct HandleCore {
   bool finalized = false;
   Tower vis, txt;
   void* wpatch = nullptr;  // [v_width, kpad] operand dtype ([v_width, 2 kpad] split)
+  void* wproj = nullptr;   // visual_projection.weight [proj_dim, v_width] in the vision tower's operand form (the local pass's projection GEMM)
   uint64_t w_inexact = 0;  // vision GEMM-weight elements that are not operand-dtype numbers (mcm_finalize_weights)
   int kpad = 0, np = 0, ntok = 0;
   // workspace
@@ -660,6 +661,14 @@ int mcm_finalize_weights(mcm_handle* h) {
   const int kreal = 3 * c.patch_size * c.patch_size;
   if (h->vis.split) HIP_TRY(h, launch_cvt_weight_split(c.precision, wp, h->wpatch, c.v_width, kreal, h->kpad, nullptr));
   else HIP_TRY(h, launch_cvt_weight(c.precision, wp, h->wpatch, c.v_width, kreal, h->kpad, nullptr));
+  {  // the projection as a GEMM operand, split where the tower's weights are (mcm_encode_image_local; the pooled rows of
+     // every other entry keep reading the fp32 master in launch_pool_project)
+    const float* wv = W(h, "visual_projection.weight");
+    const size_t wes = (size_t)prec_esize(c.precision) * (h->vis.split ? 2 : 1);
+    if ((rc = dev_alloc(h, &h->wproj, (size_t)c.proj_dim * c.v_width * wes))) return rc;
+    if (h->vis.split) HIP_TRY(h, launch_cvt_weight_split(c.precision, wv, h->wproj, c.proj_dim, c.v_width, c.v_width, nullptr));
+    else HIP_TRY(h, launch_cvt_weight(c.precision, wv, h->wproj, c.proj_dim, c.v_width, c.v_width, nullptr));
+  }
   HIP_TRY(h, hipDeviceSynchronize());
   h->finalized = true;
   return MCM_OK;
@@ -905,6 +914,124 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev, int32_t B
   hipStream_t s = (hipStream_t)stream;
   Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * ((double)K + (double)G * gs) * h->cfg.proj_dim);
   HIP_TRY(h, launch_neglabel(feats_dev, B, bank_dev, K, G, gs, h->cfg.proj_dim, T, S, work_dev, scores_dev, group_dev, s));
+  return MCM_OK;
+}
+
+// ---- GL-MCM: the local score on features, and the local features from the tower ----
+namespace {
+bool local_args_ok(const mcm_handle* h, int32_t B, int32_t R, int32_t K) {
+  return h && B >= 1 && R >= 1 && K >= 1 && (int64_t)B * R <= INT32_MAX && h->cfg.proj_dim >= 4 && h->cfg.proj_dim % 4 == 0;
+}
+
+// What a local call needs of the handle beyond an image call's own checks (0 = passed).  The local pass keeps its
+// intermediates in buffers that are dead behind launch_pool_project: out_proj's rows in h->x, their post_layernorm in
+// h->ln, the projected rows [padded rows, P] fp32 in h->hbuf; mcm_score_glmcm also the compacted rows in h->x again.
+int check_local_call(mcm_handle* h, int32_t B) {
+  const mcm_config& c = h->cfg;
+  if (h->ntok < 2 || c.v_layers < 1) return fail(h, MCM_EINVAL, "the local pass needs patch tokens and an encoder layer");
+  if (c.proj_dim % 16) return fail(h, MCM_EINVAL, "the local pass projects by a GEMM: proj_dim % 16 == 0");
+  if (c.proj_dim > c.v_width) return fail(h, MCM_EINVAL, "the local pass keeps [B, R, proj_dim] in the residual buffer: proj_dim <= v_width");
+  if ((size_t)padded_rows(h, B * h->ntok) * c.proj_dim * sizeof(float) > h->hbuf_bytes)
+    return fail(h, MCM_EINVAL, "the MLP buffer does not hold the projected token rows");
+  return MCM_OK;
+}
+
+// The local pass, behind an unchanged forward of the same B images on the same stream.  The last layer's V of all
+// B ntok rows is still in h->qkv, columns [2D, 3D) (run_layers, the `cls` branch; nothing writes h->qkv afterwards):
+//   o = W_o v + b_o          the layer's out_proj over every row, fp32 into h->x (zeroed first: the residual epilogue adds)
+//   u = post_layernorm(o)    operand dtype, h->ln
+//   y = W_proj u             a GEMM over all rows against h->wproj, fp32 into h->hbuf (zeroed first, as above)
+//   local = y / |y|          rows 1 .. ntok - 1 of every image, compacted to [B, R, P]
+// No attention mixing, no residual, no MLP: MaskCLIP's value path as the GL-MCM paper describes it.
+int local_pass(mcm_handle* h, hipStream_t s, int32_t B, float* local_dev) {
+  const mcm_config& c = h->cfg;
+  const Tower& t = h->vis;
+  const int D = c.v_width, P = c.proj_dim, M = B * h->ntok, prec = t.prec, es = prec_esize(prec);
+  const LayerW& w = t.L[t.layers - 1];
+  HIP_TRY(h, hipMemsetAsync(h->x, 0, (size_t)M * D * sizeof(float), s));
+  GemmArgs o{};
+  o.x = (const char*)h->qkv + (size_t)2 * D * es; o.w = w.wo; o.bias = w.bo; o.resid = h->x;
+  o.M = M; o.N = D; o.K = D; o.ldx = 3 * D; o.ldo = D; o.ksplit = t.split ? 1 : 0;
+  HIP_TRY(h, gemm(h, s, prec, EPI_RESID, o));
+  HIP_TRY(h, lnorm(h, s, prec, h->x, W(h, "vision_model.post_layernorm.weight"), W(h, "vision_model.post_layernorm.bias"),
+                   h->ln, M, D, false));
+  // (gemm() runs this one on whole 256-row tiles where the workspace has them: the pad rows of h->ln are zero or hold
+  // LayerNorm outputs of an earlier batch, their products land behind row M of h->hbuf and are never read)
+  HIP_TRY(h, hipMemsetAsync(h->hbuf, 0, (size_t)padded_rows(h, M) * P * sizeof(float), s));
+  GemmArgs p{};
+  p.x = h->ln; p.w = h->wproj; p.bias = nullptr; p.resid = (float*)h->hbuf;
+  p.M = M; p.N = P; p.K = D; p.ldx = D; p.ldo = P; p.ksplit = t.split ? 1 : 0;
+  HIP_TRY(h, gemm(h, s, prec, EPI_RESID, p));
+  {
+    Scope sc(h, s, MCM_KC_POOL_PROJECT, 3.0 * B * (double)(h->ntok - 1) * P);
+    HIP_TRY(h, launch_local_compact((const float*)h->hbuf, local_dev, B, h->ntok, P, s));
+  }
+  return MCM_OK;
+}
+
+int encode_image_local_impl(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, float* global_dev,
+                            float* local_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC) return fail(h, MCM_EINVAL, "unknown pixel_format");
+  int rc = check_image_call(h, pixels_dev, global_dev, B, false);
+  if (rc) return rc;
+  if (!local_dev) return fail(h, MCM_EINVAL, "null pointer");
+  if ((uintptr_t)local_dev & 15) return fail(h, MCM_EINVAL, "local_dev must be 16-byte aligned");
+  if ((rc = check_local_call(h, B))) return rc;
+  if ((rc = encode_image_impl(h, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, global_dev, stream))) return rc;
+  return local_pass(h, (hipStream_t)stream, B, local_dev);
+}
+}  // namespace
+
+int mcm_local_workspace_bytes(const mcm_handle* h, int32_t B, int32_t R, int32_t K, int64_t* bytes_out) {
+  if (!bytes_out || !local_args_ok(h, B, R, K)) return MCM_EINVAL;
+  *bytes_out = local_work_bytes(B, R);
+  return MCM_OK;
+}
+
+int mcm_local_score_features(mcm_handle* h, const float* local_dev, int32_t B, int32_t R, const float* text_dev, int32_t K,
+                             float T, void* work_dev, int64_t work_bytes, float* local_scores_dev, float* patch_dev,
+                             void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!local_dev || !text_dev || !work_dev || !local_scores_dev || !local_args_ok(h, B, R, K))
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (((uintptr_t)local_dev | (uintptr_t)text_dev) & 15) return fail(h, MCM_EINVAL, "local_dev / text_dev must be 16-byte aligned");
+  if (((uintptr_t)work_dev | (uintptr_t)local_scores_dev | (uintptr_t)patch_dev) & 3)
+    return fail(h, MCM_EINVAL, "work_dev / local_scores_dev / patch_dev must be 4-byte aligned");
+  if (work_bytes < local_work_bytes(B, R)) return fail(h, MCM_EINVAL, "work_bytes is below mcm_local_workspace_bytes");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * (double)R * (double)K * h->cfg.proj_dim);
+  HIP_TRY(h, launch_local_score(local_dev, B, R, text_dev, K, h->cfg.proj_dim, T, work_dev, local_scores_dev, patch_dev, s));
+  return MCM_OK;
+}
+
+int mcm_encode_image_local(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, float* global_dev,
+                           float* local_dev, void* stream) {
+  return encode_image_local_impl(h, pixels_dev, pixel_format, B, global_dev, local_dev, stream);
+}
+
+int mcm_score_glmcm(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, const float* text_dev, int32_t K,
+                    float T, float lambda, float* scores_dev, float* global_scores_dev, float* local_scores_dev,
+                    float* patch_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!text_dev || !scores_dev) return fail(h, MCM_EINVAL, "null pointer");
+  if (K < 1 || !(T > 0.f) || !std::isfinite(T) || !std::isfinite(lambda)) return fail(h, MCM_EINVAL, "bad K / T / lambda");
+  if ((uintptr_t)text_dev & 15) return fail(h, MCM_EINVAL, "text_dev must be 16-byte aligned");
+  // the compacted local rows go where out_proj's rows were (h->x is dead again behind post_layernorm: B R P <= B ntok D
+  // floats, check_local_call); the row values and the parts nobody asked for go to h->att, which is dead as well
+  const int R = h->ntok - 1;
+  float* local = h->x;
+  int rc = encode_image_local_impl(h, pixels_dev, pixel_format, B, h->feat, local, stream);
+  if (rc) return rc;
+  float* work = (float*)h->att;  // [B R] row values, then [B] and [B]: B (R + 2) floats <= the B ntok D operand elements it holds
+  float* gs = global_scores_dev ? global_scores_dev : work + (size_t)B * R;
+  float* ls = local_scores_dev ? local_scores_dev : work + (size_t)B * R + B;
+  if ((rc = mcm_score_features(h, h->feat, B, text_dev, K, T, MCM_SCORE_MCM, gs, stream))) return rc;
+  if ((rc = mcm_local_score_features(h, local, B, R, text_dev, K, T, work, local_work_bytes(B, R), ls, patch_dev, stream))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B);
+  HIP_TRY(h, launch_local_combine(gs, ls, lambda, scores_dev, B, s));
   return MCM_OK;
 }
 

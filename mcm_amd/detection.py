@@ -139,39 +139,66 @@ def get_ood_scores_clip(args, net, loader, test_labels, in_dist=False, device_ou
     if not hasattr(net, "score_images"):
         raise TypeError("net must be a mcm_amd NativeCLIP (fused score_images path); "
                         "there is no eager fallback")
-    rank, ws = mdist.world()
-    n_total = len(loader.dataset)
     with torch.no_grad():
         text_features = prompt_bank(args, net, test_labels)
-        by_index = True  # this rank's shard is the contiguous index range shard_range gives
-        mine = lambda i: True  # noqa: E731
-        batches = loader
-        if ws > 1:
-            lo, hi = mdist.shard_range(n_total, rank, ws)
-            batches = shard_loader(loader, lo, hi)
-            if batches is None:  # an opaque iterable: batch-range shards (every rank still pays its decode)
-                by_index = False
-                nb = len(loader)
-                blo, bhi = mdist.shard_range(nb, rank, ws)
-                batches = loader
-                mine = lambda i: blo <= i < bhi  # noqa: E731
-        parts = []
-        for batch_idx, (images, _labels) in enumerate(batches):
-            if not mine(batch_idx):
-                continue
-            parts.append(net.score_images(images, text_features, float(args.T), args.score))
-        local = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32,
-                                                           device=text_features.device)
-        if mdist.group_active():  # (also a 1-rank group: the collective really runs — RCCL on a GPU box)
-            if by_index:
-                full = mdist.all_gather_scores(local, n_total)
-            else:  # batch-range shards of an opaque loader: sizes follow the batch split
-                full = _gather_batch_shards(local, n_total, ws)
-        else:
-            full = local
+        return _scores_over_shards(loader, text_features.device, device_out,
+                                   lambda images: net.score_images(images, text_features, float(args.T), args.score))
+
+
+def _scores_over_shards(loader, device, device_out, score_batch):
+    """The sharding and gathering of `get_ood_scores_clip`, for any per-batch score `score_batch(images) -> [b]` device
+    tensor: this rank's contiguous index shard of `loader.dataset` (batch-range shards where the loader cannot be split by
+    index), all-gathered in dataset order where a process group exists.  Call under `torch.no_grad()`.  Returns the
+    [len(loader.dataset)] scores as a device tensor (`device_out`) or a float32 ndarray."""
+    import torch
+
+    rank, ws = mdist.world()
+    n_total = len(loader.dataset)
+    by_index = True  # this rank's shard is the contiguous index range shard_range gives
+    mine = lambda i: True  # noqa: E731
+    batches = loader
+    if ws > 1:
+        lo, hi = mdist.shard_range(n_total, rank, ws)
+        batches = shard_loader(loader, lo, hi)
+        if batches is None:  # an opaque iterable: batch-range shards (every rank still pays its decode)
+            by_index = False
+            nb = len(loader)
+            blo, bhi = mdist.shard_range(nb, rank, ws)
+            batches = loader
+            mine = lambda i: blo <= i < bhi  # noqa: E731
+    parts = []
+    for batch_idx, (images, _labels) in enumerate(batches):
+        if not mine(batch_idx):
+            continue
+        parts.append(score_batch(images))
+    local = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=device)
+    if mdist.group_active():  # (also a 1-rank group: the collective really runs — RCCL on a GPU box)
+        if by_index:
+            full = mdist.all_gather_scores(local, n_total)
+        else:  # batch-range shards of an opaque loader: sizes follow the batch split
+            full = _gather_batch_shards(local, n_total, ws)
+    else:
+        full = local
     if device_out:
         return full.detach()[:n_total]
     return full.detach().cpu().numpy().astype(np.float32, copy=False)[:n_total].copy()
+
+
+def get_glmcm_scores(args, net, loader, test_labels, device_out=False):
+    """`--score GL-MCM` (Miyai et al.): per sample -(S_G + lambda S_L) against the concept bank `test_labels`, S_G the MCM
+    term of the global feature and S_L the best softmax match of any single patch's local feature
+    (`net.score_images_glmcm`); reads `args.T` and `args.gl_lambda` (default 1).  Larger = more OOD.  The
+    prompt bank, the per-rank index shards and the all-gather are those of `get_ood_scores_clip`; every sample is scored.
+    Returns a float32 ndarray [len(loader.dataset)], or the device tensor with `device_out=True`."""
+    import torch
+
+    if not hasattr(net, "score_images_glmcm"):
+        raise TypeError("get_glmcm_scores needs a net with score_images_glmcm (a NativeCLIP); there is no eager fallback")
+    lam = float(getattr(args, "gl_lambda", 1.0))
+    with torch.no_grad():
+        text_features = prompt_bank(args, net, test_labels)
+        return _scores_over_shards(loader, text_features.device, device_out,
+                                   lambda images: net.score_images_glmcm(images, text_features, float(args.T), lam))
 
 
 def get_ood_predictions_clip(args, net, loader, test_labels, topk=5, device_out=False):

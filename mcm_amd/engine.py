@@ -150,6 +150,10 @@ def load_library(harness: bool = False):
     L.mcm_knn_score_features.argtypes = [vp, vp, i32, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
     L.mcm_neglabel_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
     L.mcm_neglabel_score_features.argtypes = [vp, vp, i32, vp, i32, i32, i32, ctypes.c_float, i32, vp, ctypes.c_int64, vp, vp, vp]
+    L.mcm_local_workspace_bytes.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
+    L.mcm_local_score_features.argtypes = [vp, vp, i32, i32, vp, i32, ctypes.c_float, vp, ctypes.c_int64, vp, vp, vp]
+    L.mcm_encode_image_local.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.mcm_score_glmcm.argtypes = [vp, vp, i32, i32, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp]
     L.mcm_measures.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, ctypes.c_double,
                                ctypes.POINTER(ctypes.c_double), vp]
     L.mcm_saturation_check.argtypes = [vp, i32]
@@ -178,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "mcm_maha_fit_accumulate",
     "mcm_knn_workspace_bytes", "mcm_knn_score_features",
     "mcm_neglabel_workspace_bytes", "mcm_neglabel_score_features",
+    "mcm_local_workspace_bytes", "mcm_local_score_features", "mcm_encode_image_local", "mcm_score_glmcm",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -446,6 +451,87 @@ class NativeCLIP:
                              f"splits={splits}: B, n_id, group_size >= 1, 1 <= groups <= 1024, T > 0 and finite, "
                              "0 <= splits <= 32 and proj_dim % 4 == 0 are required")
         self._check(rc)
+
+    # -- GL-MCM: the local (patch-level) term next to MCM (include/mcm.h mcm_score_glmcm) -------------------
+    @property
+    def local_rows(self) -> int:
+        """R: patch tokens per image, the rows of an image's local features."""
+        return (self.geo.image_size // self.geo.patch_size) ** 2
+
+    def _no_x2_local(self, what):
+        if self.x2_default:
+            raise ValueError(f"{what}: the split-activation arm (precision='fp16x2') has no local pass")
+
+    def get_local_features(self, pixel_values):
+        """[b,3,S,S] fp32 (or [b,S,S,3] uint8) → (global [b,P], local [b,R,P]) fp32, unit-norm rows: the global feature of
+        `get_image_features(..., normalize=True)` (the same bits) and, per patch token, the last layer's value path
+        (layer_norm1 → v_proj → out_proj → post_layernorm → visual_projection; include/mcm.h mcm_encode_image_local)."""
+        import torch
+
+        self._no_x2_local("get_local_features")
+        px = self._pixels(pixel_values)
+        fmt = 1 if px.dtype == torch.uint8 else 0
+        b, R, P = px.shape[0], self.local_rows, self.geo.proj_dim
+        glob = torch.empty((b, P), device=self.device, dtype=torch.float32)
+        loc = torch.empty((b, R, P), device=self.device, dtype=torch.float32)
+        for s in range(0, b, self.max_batch):
+            n = min(self.max_batch, b - s)
+            self._check(self._lib.mcm_encode_image_local(self._h, px[s:s + n].data_ptr(), fmt, n, glob[s:s + n].data_ptr(),
+                                                         loc[s:s + n].data_ptr(), _stream_ptr()))
+        return glob, loc
+
+    def local_scores(self, local, text_features, T: float = 1.0, return_patches: bool = False):
+        """local [B,R,P] + bank [K,P] fp32 (device) → [B] fp32: -S_L, S_L = max over the R rows of max_k softmax_k(row · bank / T)
+        (include/mcm.h mcm_local_score_features); larger = more OOD.  `return_patches=True`: (scores, patch [B,R]), every
+        row's largest softmax probability."""
+        import torch
+
+        loc = local.to(device=self.device, dtype=torch.float32).contiguous()
+        t = self._bank(text_features)
+        if loc.dim() != 3 or loc.shape[2] != self.geo.proj_dim or loc.shape[0] == 0 or loc.shape[1] == 0:
+            raise ValueError(f"local must be [B,R,{self.geo.proj_dim}] with B, R >= 1, got {tuple(loc.shape)}")
+        B, R, K, T = int(loc.shape[0]), int(loc.shape[1]), int(t.shape[0]), float(T)
+        need = ctypes.c_int64(0)
+        self._check_local(self._lib.mcm_local_workspace_bytes(self._h, B, R, K, ctypes.byref(need)), B, R, K, T)
+        work = getattr(self, "_local_work", None)
+        if work is None or work.numel() * 4 < need.value:
+            work = self._local_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
+        scores = torch.empty(B, device=self.device, dtype=torch.float32)
+        patch = torch.empty((B, R), device=self.device, dtype=torch.float32) if return_patches else None
+        self._check_local(self._lib.mcm_local_score_features(
+            self._h, loc.data_ptr(), B, R, t.data_ptr(), K, T, work.data_ptr(), work.numel() * 4, scores.data_ptr(),
+            patch.data_ptr() if return_patches else None, _stream_ptr()), B, R, K, T)
+        return (scores, patch) if return_patches else scores
+
+    def _check_local(self, rc, B, R, K, T):
+        if rc == -1:
+            raise ValueError(f"local_scores: refused (rc={rc}) for B={B}, R={R}, K={K}, T={T}: B, R, K >= 1, B R < 2^31, "
+                             "T > 0 and finite and proj_dim % 4 == 0 are required")
+        self._check(rc)
+
+    def score_images_glmcm(self, pixel_values, text_features, T: float = 1.0, lam: float = 1.0, return_parts: bool = False):
+        """pixels + pre-encoded bank [K,P] → the GL-MCM score [b] fp32 on the device: -(S_G + lam S_L), S_G the MCM term of
+        the global feature (the bits of `score_images(..., "MCM")`), S_L the local term of `local_scores` on this image's
+        patch rows (include/mcm.h mcm_score_glmcm); larger = more OOD.  `return_parts=True`: (scores, -S_G [b], -S_L [b],
+        patch [b,R])."""
+        import torch
+
+        self._no_x2_local("score_images_glmcm")
+        px = self._pixels(pixel_values)
+        fmt = 1 if px.dtype == torch.uint8 else 0
+        t = self._bank(text_features)
+        b, R = px.shape[0], self.local_rows
+        out = torch.empty(b, device=self.device, dtype=torch.float32)
+        gs = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
+        ls = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
+        patch = torch.empty((b, R), device=self.device, dtype=torch.float32) if return_parts else None
+        for s in range(0, b, self.max_batch):
+            n = min(self.max_batch, b - s)
+            self._check(self._lib.mcm_score_glmcm(
+                self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T), float(lam), out[s:s + n].data_ptr(),
+                gs[s:s + n].data_ptr() if return_parts else None, ls[s:s + n].data_ptr() if return_parts else None,
+                patch[s:s + n].data_ptr() if return_parts else None, _stream_ptr()))
+        return (out, gs, ls, patch) if return_parts else out
 
     def get_text_features(self, input_ids, attention_mask=None, normalize: bool = False):
         """[K,S] ids → [K,P] fp32: HF `get_text_features` (the text projection output; unit-norm rows
