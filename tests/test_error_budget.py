@@ -9,7 +9,11 @@ budgets, rows of magnitude 2^-12 ... 2^-4 included; each planted mistake breaks 
 last K-step, X_lo paired with the next K-step's W, a subnormal lo flushed on the operand or the output side, the output's
 lo dropped, K_hi Q_lo or V_hi P_lo dropped, P split without its 2^12 scale (on error_budget.coherent_small_p_qkv), W_lo
 dropped.  EPI_GELU_X2 computed with quick_gelu_fast is the one listed mistake no input within the op's contract shows: it
-is pinned as undetectable (test_gelu_fast_in_the_split_epilogue_stays_inside_the_budget)."""
+is pinned as undetectable (test_gelu_fast_in_the_split_epilogue_stays_inside_the_budget).
+
+The causal mask (test_gpu_text_lengths.py sweeps every prompt length 1 ... 77 under attention_budget): the correct emulation
+stays inside the budget on both sides of every key-tile boundary, and each of three wrong masks (one future key visible, the
+diagonal tile taken as full, the diagonal excluded) breaks it at EVERY length 2 ... 77."""
 import numpy as np
 import pytest
 
@@ -257,16 +261,31 @@ def test_layernorm_emulation_within_budget_and_single_pass_breaks_it(D, out):
 
 
 # ---- attention emulation -----------------------------------------------------------------------------------------------
-def _attn_emulate(q, k, v, causal, out, rowsum="fp32", p_bits=None):
+CAUSAL_MASK_MISTAKES = ("future_key", "diag_tile_full", "no_diagonal")
+
+
+def _causal_mask(L, mask=None):
+    """[q, key] visibility of the causal kernels, `key < L && key <= q` (attention.hip mask_tile; jmax = q + 1 in the fp32
+    kernel), or one of CAUSAL_MASK_MISTAKES: "future_key" (key <= q + 1: one future key visible), "diag_tile_full" (the
+    16-key tile that holds the diagonal taken as a full tile: key < (q // 16 + 1) * 16), "no_diagonal" (key < q: row 0 is
+    left with no key at all)."""
+    q, key = np.arange(L)[:, None], np.arange(L)[None, :]
+    if mask is None:
+        return key <= q
+    return {"future_key": key <= q + 1, "diag_tile_full": key < (q // 16 + 1) * 16, "no_diagonal": key < q}[mask]
+
+
+def _attn_emulate(q, k, v, causal, out, rowsum="fp32", p_bits=None, mask=None):
     """One (sequence, head) as the kernels do it: S = K Q^T with fp32 accumulation, m = row max, e = exp2(s*SC - m*SC)
     (fp32 argument), P = e rounded to the operand format, O = P V (fp32 accumulation) / rowsum.  rowsum "fp32": over the
     fp32 e (attn_bf16_kernel); "P": over the rounded P (attn_tr_kernel's all-ones MFMA); "16bit": a mistake, the row sum
-    accumulated in the 16-bit format.  p_bits: P rounded to that many significand bits instead (a mistake)."""
+    accumulated in the 16-bit format.  p_bits: P rounded to that many significand bits instead (a mistake).  mask: one of
+    CAUSAL_MASK_MISTAKES in place of the causal mask (a mistake; a row left without keys comes out NaN)."""
     L = q.shape[0]
     SC = F32(0.125 * 1.4426950408889634)
     s = (torch.from_numpy(_f32(k)) @ torch.from_numpy(_f32(q)).T).numpy().T    # [q, key], fp32
     if causal:
-        s = np.where(np.tril(np.ones((L, L), bool)), s, -np.inf).astype(F32)
+        s = np.where(_causal_mask(L, mask), s, -np.inf).astype(F32)
     m = s.max(axis=1, keepdims=True)
     with np.errstate(invalid="ignore"):
         arg = _f32(s.astype(np.float64) * SC - _f32(m * SC))
@@ -293,7 +312,8 @@ def _attn_emulate(q, k, v, causal, out, rowsum="fp32", p_bits=None):
         for j in range(L):
             ls = eb.round_to(ls + p[:, j:j + 1], out)
     o = (torch.from_numpy(p) @ torch.from_numpy(_f32(v))).numpy()
-    o = _f32(o * _f32(F32(1) / ls))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        o = _f32(o * _f32(F32(1) / ls))
     return o if out == "fp32" else eb.round_to(o, out)
 
 
@@ -310,6 +330,8 @@ def _attn_case(L, out, seed, spiked=False):
 
 
 ATTN_L = [(1, False), (2, False), (17, False), (50, False), (77, True), (197, False), (197, "spiked")]
+# causal lengths on both sides of every key-tile boundary the text tower's 1 ... 77 tokens cross (NT = 1 ... 5)
+ATTN_L += [(L, True) for L in (1, 2, 15, 16, 17, 31, 32, 33, 48, 49, 63, 64, 65, 76)]
 
 
 @pytest.mark.parametrize("out", ["bf16", "fp16", "fp32"])
@@ -335,6 +357,27 @@ def test_attention_mutations_break_the_budget(mutation, out):
         worst = max(worst, eb.worst(got, ref, bud)[0])
     print(f"attention {mutation} {out}: worst budget ratio {worst:.3g}")
     assert worst > 1.0
+
+
+@pytest.mark.parametrize("out", ["bf16", "fp16", "fp32"])
+@pytest.mark.parametrize("mutation", CAUSAL_MASK_MISTAKES)
+def test_causal_mask_mutations_break_the_budget(mutation, out):
+    """Each wrong causal mask, with the kernels' own rounding emulated, misses the budget at EVERY length 2 ... 77 and in
+    both row-sum forms, not only at the worst of a list: a mask that is wrong at one untested length only cannot hide (at
+    L = 1 none of the three can show: one query, one key).  "no_diagonal" leaves row 0 without a key (NaN, an infinite
+    ratio); its ratio is taken over rows 1 ... so that the figure says what the visible rows show."""
+    low = (np.inf, None)
+    for L in range(2, 78):
+        q, k, v = _attn_case(L, out, L)
+        ref, bud = eb.attention_budget(q, k, v, True, out)
+        rows = slice(1, None) if mutation == "no_diagonal" else slice(None)
+        for rowsum in (("fp32", "P") if out != "fp32" else ("fp32",)):
+            assert eb.worst(_attn_emulate(q, k, v, True, out, rowsum=rowsum), ref, bud)[0] <= 1.0, (L, rowsum)
+            got = _attn_emulate(q, k, v, True, out, rowsum=rowsum, mask=mutation)
+            r = eb.worst(got[rows], ref[rows], bud[rows])[0]
+            assert r > 1.0, (mutation, out, L, rowsum, r)
+            low = min(low, (r, L))
+    print(f"MUTATION causal-mask {mutation} {out}: smallest budget ratio over L = 2 ... 77: {low[0]:.3g} at L={low[1]}")
 
 
 # ---- scores ------------------------------------------------------------------------------------------------------------
