@@ -54,7 +54,7 @@ def process_args(argv=None):
                             "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
-                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel", "GL-MCM"], help="score options")
+                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel", "GL-MCM", "vim"], help="score options")
     # Mahalanobis baseline (--score maha), reference eval_ood_detection.py:38-44
     p.add_argument("--feat_dim", type=int, default=512)
     p.add_argument("--normalize", type=bool, default=False)
@@ -137,6 +137,12 @@ def process_args(argv=None):
     p.add_argument("--gl-lambda", default=1.0, type=float, metavar="L",
                    help="--score GL-MCM (Miyai et al.: MCM plus a local term, the best softmax match of any single image patch's "
                         "value-path feature): the score is -(S_G + L S_L); default 1")
+    p.add_argument("--vim-dim", default=0, type=int, metavar="D",
+                   help="--score vim (ViM, Wang et al. 2022: alpha x the norm of an image's unit-norm feature outside the principal "
+                        "subspace of the training features, minus the energy of its logits): the principal dimension D, "
+                        "1..proj_dim - 1; 0 (default) = proj_dim // 2 below 768, 512 for 768 <= proj_dim < 2048, 1000 above.  The "
+                        "training set is the \"train\" set (--subset / --max_count as for --score knn), every rank fitting its shard")
+    p.add_argument("--vim-T", default=0.01, type=float, help="--score vim: the temperature of the logits (--T is ignored there)")
     args = p.parse_args(argv)
     if args.score == "GL-MCM":
         if not np.isfinite(args.gl_lambda):
@@ -157,10 +163,17 @@ def process_args(argv=None):
             p.error("--neg-groups G: G must be 1..1024")
         if not (args.neg_T > 0.0 and np.isfinite(args.neg_T)):
             p.error("--neg-T must be positive and finite")
+    if args.score == "vim":
+        if args.vim_dim < 0:
+            p.error("--vim-dim D: D must be 0 or 1..proj_dim - 1")
+        if not (args.vim_T > 0.0 and np.isfinite(args.vim_T)):
+            p.error("--vim-T must be positive and finite")
     if not 0 <= args.knn_k <= 1024:
         p.error("--knn-k K: K must be 1..1024 (0 = chosen from the bank size)")
-    if args.score in ("knn", "neglabel") and args.refine_threshold in ("on", "exact"):
+    if args.score in ("knn", "neglabel", "vim") and args.refine_threshold in ("on", "exact"):
         p.error("--refine-threshold on needs a 16-bit --dtype and an MCM-family --score")
+    if args.score == "vim":
+        args.refine_threshold = "off"  # auto resolves to off
     if args.maha_fit == "device" and args.score != "maha":
         p.error("--maha-fit device needs --score maha (no other score fits anything)")
     if args.predict:
@@ -169,6 +182,8 @@ def process_args(argv=None):
                     "baselines (--score maha, --score knn) have no prompt bank to match against")
         if args.score == "neglabel":
             p.error("--predict is not available with --score neglabel (its kernel returns group masses, not matched concepts)")
+        if args.score == "vim":
+            p.error("--predict is not available with --score vim (its kernel returns a residual and an energy, not matched concepts)")
         if not 1 <= args.predict <= 8:
             p.error("--predict K: K must be 1..8")
     if args.decoder:
@@ -306,8 +321,9 @@ def main(argv=None):
     # images, for which half the batch costs nothing extra; otherwise the workspace is not allocated at all
     # the training-set baselines (no prompt bank) and neglabel (a bank of its own): scores come back as host arrays, and
     # there is no threshold refinement
-    # (GL-MCM uses the prompt bank, but like them has no re-scoring arm and hands back host arrays)
-    no_bank = args.score in ("maha", "knn", "neglabel", "GL-MCM")
+    # (GL-MCM uses the prompt bank, and vim the prompt bank with a basis behind it, but like them they have no re-scoring
+    # arm and hand back host arrays)
+    no_bank = args.score in ("maha", "knn", "neglabel", "GL-MCM", "vim")
     will_refine = args.refine_threshold != "off" and not no_bank
     x2_batch = 0 if args.dtype == "fp16x2" else (max(1, args.batch_size // 2) if (args.dtype == "fp16" and will_refine) else -1)
     net = build_model(args.CLIP_ckpt, weights=args.weights, device=dev, precision=args.dtype,
@@ -395,6 +411,27 @@ def main(argv=None):
                   f"M = {neg_bank['M']} kept, G = {neg_bank['G']} groups of gs = {neg_bank['gs']}; kept d from "
                   f"{float(neg_bank['d'].min()):.6f} to {float(neg_bank['d'].max()):.6f} (quantile {args.neg_quantile})")
         in_score = get_neglabel_score(args, net, test_loader, neg_bank)
+    elif args.score == "vim":
+        from mcm_amd.detection import get_vim_fit, get_vim_score, vim_principal_dim
+
+        try:  # the geometry is known here
+            vim_principal_dim(net.geo.proj_dim, args.vim_dim)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        log.debug(f"--score vim: --T {args.T} is ignored; the temperature of the logits is --vim-T {args.vim_T}")
+        n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
+        try:
+            vim_fit = get_vim_fit(args, net, _loader(args, net, "train", n_train, False, sources), test_labels)
+        except ValueError as e:  # the subspace is not determined, or alpha is not a number
+            raise SystemExit(str(e))
+        lam = vim_fit["eigenvalues"]
+        log.debug(f"--score vim: D = {vim_fit['D']}{'' if args.vim_dim else ' (auto)'}, R = {vim_fit['R']}, n = {vim_fit['n']} unit-norm "
+                  f"training features ({sources['train']['kind']}), alpha = {vim_fit['alpha']:.6g}, lambda_D = {lam[vim_fit['R']]:.6e}, "
+                  f"lambda_(D+1) = {lam[vim_fit['R'] - 1]:.6e}, lambda_max = {lam[-1]:.6e}")
+        if vim_fit["alpha"] <= 0.0:
+            log.debug("NOTE: alpha is not positive, so the residual enters the score with the wrong sign (seeded synthetic weights "
+                      "can produce this; a trained checkpoint should not)")
+        in_score = get_vim_score(args, net, test_loader, vim_fit)
     elif args.score == "GL-MCM":
         from mcm_amd.detection import get_glmcm_scores
 
@@ -445,6 +482,8 @@ def main(argv=None):
             out_score = get_knn_score(args, net, ood_loader, knn_bank, knn_k)
         elif args.score == "neglabel":
             out_score = get_neglabel_score(args, net, ood_loader, neg_bank)
+        elif args.score == "vim":
+            out_score = get_vim_score(args, net, ood_loader, vim_fit)
         elif args.score == "GL-MCM":
             out_score = get_glmcm_scores(args, net, ood_loader, test_labels)
         else:

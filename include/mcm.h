@@ -45,7 +45,8 @@ extern "C" {
                           * (still 5) mcm_knn_workspace_bytes / mcm_knn_score_features: two added symbols, on the same terms
                           * (still 5) mcm_neglabel_workspace_bytes / mcm_neglabel_score_features: two added symbols, on the same terms
                           * (still 5) mcm_local_workspace_bytes / mcm_local_score_features / mcm_encode_image_local /
-                          * mcm_score_glmcm: four added symbols, on the same terms */
+                          * mcm_score_glmcm: four added symbols, on the same terms
+                          * (still 5) mcm_vim_workspace_bytes / mcm_vim_score_features: two added symbols, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -439,6 +440,44 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev /* [B, pro
                                 const float* bank_dev /* [K + G gs, proj_dim] */, int32_t K, int32_t G, int32_t gs,
                                 float T, int32_t splits, void* work_dev, int64_t work_bytes,
                                 float* scores_dev /* [B] */, float* group_dev /* [B, G] or NULL */, void* stream);
+
+/* ---- virtual-logit matching (--score vim; Wang et al., CVPR 2022) --------------------------------------
+ * The third training-set score: the norm of a feature row's component outside the training features' principal
+ * subspace, scaled to logit units, minus the energy of its zero-shot logits (added under ABI 5: two symbols only).
+ * P = the handle's proj_dim, everything row-major:
+ *   bank_dev [N, P]  rows [0, K) are the prompts, rows [K, K + R) the rows of the null-space basis NS (orthonormal, the
+ *                    eigenvectors of the R smallest eigenvalues of the training features' uncentred second moment);
+ *                    N = K + R, which must fit int32;
+ *   s[b, n]          = the fp32 dot product of feats_dev[b] and bank_dev[n] as mcm_knn_score_features defines it (the
+ *                    exact-fp32 MFMA: one rounding per product, operands never narrowed);
+ *   resid[b]         = sqrt(sum_{j < R} ((double) s[b, K + j] - off_dev[j])^2); off_dev [R] fp64 is the projection of the
+ *                    head's origin on NS (o . NS_j; NULL = 0, the zero-shot head: it has no bias);
+ *   lse[b]           = logsumexp_{k < K} s[b, k] / T,   maxlogit[b] = max_{k < K} s[b, k] / T (NaN entries skipped);
+ *   scores[b]        = (float) ((double) alpha resid[b] - lse[b]); larger = more OOD, the sign every stored score here has;
+ *   parts_dev[b, :]  = resid[b], lse[b], maxlogit[b] rounded to fp32 (optional: what a fit needs to form alpha).
+ * A NaN similarity anywhere in a row makes that row's score NaN; other rows are unaffected.
+ * The [B, N] similarities exist in registers and LDS only.  The bank is cut into `splits` contiguous ranges of
+ * ceil(N / splits) rows (the last ones may be short or empty); each keeps per query one 16-byte slot in work_dev
+ * ([splits, B] slots): the online-softmax pair (max, sum of exp((s - max) / T); the sum carried in fp64, stored as fp32)
+ * of its prompt rows and the fp64 sum of squares of its basis rows; a second launch combines them in split order in
+ * fp64.  Only the slots the first launch wrote are read (which those are follows from K, R and the split length), so
+ * work_dev needs no initialisation.  splits = 0: the library chooses from B, N and the device's CU count; n > 0:
+ * exactly n, at most MCM_KNN_MAX_SPLITS.  For fixed arguments (splits included) the outputs are the same bits on every
+ * run, for every cut of the queries into calls and every row position (no atomics, no workgroup waits for another);
+ * across `splits` the sums are associated differently and the results agree to rounding, not bit for bit.
+ * mcm_vim_workspace_bytes: *bytes_out = the work_dev size the score call needs for the same (B, K, R, splits); with
+ * splits = 0 it resolves the split count on the CURRENT device, as the score call does.
+ * Asynchronous on `stream`, no allocation, no host synchronisation; timed under MCM_KC_SCORE (2 B N P flop).
+ * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
+ * B, K or R < 1, K + R above INT32_MAX, T <= 0 or not finite, alpha not finite, splits < 0 or > MCM_KNN_MAX_SPLITS,
+ * work_bytes below mcm_vim_workspace_bytes, proj_dim % 4 != 0, feats_dev / bank_dev not 16-byte aligned, or off_dev /
+ * work_dev not 8-byte aligned.  off_dev and parts_dev may be NULL. */
+int mcm_vim_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t R, int32_t splits, int64_t* bytes_out);
+int mcm_vim_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
+                           const float* bank_dev /* [K + R, proj_dim]: prompts, then basis rows */, int32_t K, int32_t R,
+                           const double* off_dev /* [R] or NULL */, float T, float alpha, int32_t splits,
+                           void* work_dev, int64_t work_bytes, float* scores_dev /* [B] */,
+                           float* parts_dev /* [B, 3] = resid, lse, maxlogit as fp32, or NULL */, void* stream);
 
 /* ---- GL-MCM: a patch-level local score next to MCM (--score GL-MCM; Miyai et al.) ---------------------
  * score = -(S_G + lambda S_L): S_G the MCM term of the global (CLS) feature, S_L the best concept match of any single

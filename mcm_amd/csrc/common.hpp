@@ -436,6 +436,14 @@ int64_t neglabel_work_bytes(int B, int G, int S);
 hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, int G, int gs, int P, float T, int S,
                            void* work, float* scores, float* group, hipStream_t s);
 
+// vim.hip: the ViM score of every feats row against bank [K + R, P] (rows [0, K) the prompts, then the R rows of the
+// null-space basis): scores [B] = alpha resid - lse, resid = sqrt(sum_j (s[b, K + j] - off[j])^2) (off [R] fp64 or nullptr = 0),
+// lse = logsumexp_k s[b, k] / T; parts [B, 3] (or nullptr) = resid, lse, max_k s[b, k] / T.  work holds vim_work_bytes(B, S):
+// one 16-byte slot per (split, query).
+int64_t vim_work_bytes(int B, int S);
+hipError_t launch_vim(const float* feats, int B, const float* bank, int K, int R, int P, const double* off, float T,
+                      float alpha, int S, void* work, float* scores, float* parts, hipStream_t s);
+
 // glmcm.hip: the local term of GL-MCM over patch rows [B, R, P] against bank [K, P]: patch [B, R] (or nullptr) = the
 // largest softmax probability of every row at temperature T, scores [B] = -max over an image's rows (NaN if a row's is).
 // work holds local_work_bytes(B, R): the row values.

@@ -917,6 +917,38 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev, int32_t B
   return MCM_OK;
 }
 
+// ---- ViM: null-space residual plus energy in one bank walk ----
+namespace {
+bool vim_ok(int32_t K, int32_t R) { return K >= 1 && R >= 1 && (int64_t)K + (int64_t)R <= INT32_MAX; }
+}  // namespace
+
+int mcm_vim_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t R, int32_t splits, int64_t* bytes_out) {
+  int S = 0;
+  if (!bytes_out || !bank_args_ok(h, vim_ok(K, R), B, (int64_t)K + (int64_t)R, splits, &S)) return MCM_EINVAL;
+  *bytes_out = vim_work_bytes(B, S);
+  return MCM_OK;
+}
+
+int mcm_vim_score_features(mcm_handle* h, const float* feats_dev, int32_t B, const float* bank_dev, int32_t K, int32_t R,
+                           const double* off_dev, float T, float alpha, int32_t splits, void* work_dev, int64_t work_bytes,
+                           float* scores_dev, float* parts_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  int S = 0;
+  if (!feats_dev || !bank_dev || !work_dev || !scores_dev ||
+      !bank_args_ok(h, vim_ok(K, R), B, (int64_t)K + (int64_t)R, splits, &S))
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (!std::isfinite(alpha)) return fail(h, MCM_EINVAL, "alpha must be finite");
+  if (((uintptr_t)off_dev | (uintptr_t)work_dev) & 7) return fail(h, MCM_EINVAL, "off_dev / work_dev must be 8-byte aligned");
+  if (int rc = bank_buffers(h, feats_dev, bank_dev, work_bytes, vim_work_bytes(B, S),
+                            "work_bytes is below mcm_vim_workspace_bytes"))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * ((double)K + (double)R) * h->cfg.proj_dim);
+  HIP_TRY(h, launch_vim(feats_dev, B, bank_dev, K, R, h->cfg.proj_dim, off_dev, T, alpha, S, work_dev, scores_dev, parts_dev, s));
+  return MCM_OK;
+}
+
 // ---- GL-MCM: the local score on features, and the local features from the tower ----
 namespace {
 bool local_args_ok(const mcm_handle* h, int32_t B, int32_t R, int32_t K) {

@@ -672,6 +672,117 @@ def get_neglabel_score(args, net, loader, bank_info):
     return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
 
 
+def vim_principal_dim(P, D=0):
+    """The principal dimension of `--score vim` at feature width P: `D` when given, else the paper's rule — P // 2 below 768,
+    512 for 768 <= P < 2048, 1000 above.  1 <= D < P is required (the null space keeps R = P - D >= 1 rows)."""
+    P, D = int(P), int(D or 0)
+    if D == 0:
+        D = P // 2 if P < 768 else (512 if P < 2048 else 1000)
+    if not 1 <= D < P:
+        raise ValueError(f"--vim-dim D: D must be 0 or 1..proj_dim - 1 (D = {D}, proj_dim = {P})")
+    return D
+
+
+def vim_null_space(gram, n, D):
+    """The null-space basis of ViM from gram = sum_i x_i x_i^T (fp64 [P,P]) of n rows, on the host in fp64: the eigenpairs of
+    M = gram / n (`torch.linalg.eigh`, ascending), NS [R,P] = the eigenvectors of the R = P - D smallest eigenvalues as rows,
+    rounded to fp32.  Returns (NS, eigenvalues [P] fp64 ascending: lambda_max = [-1], lambda_D = [R], lambda_{D+1} = [R - 1]).
+    Refused where the subspace is not determined: lambda_D - lambda_{D+1} <= 64 eps_fp64 lambda_max (a training set of fewer
+    than D rows is such a case: both are zero up to rounding)."""
+    import torch
+
+    M = torch.as_tensor(gram, dtype=torch.float64).detach().cpu()
+    P = int(M.shape[0])
+    n, D = int(n), int(D)
+    if M.shape != (P, P) or n < 1 or not 1 <= D < P:
+        raise ValueError(f"vim_null_space: gram {tuple(M.shape)}, n = {n}, D = {D}: a square gram, n >= 1 and 1 <= D < P are required")
+    R = P - D
+    lam, vec = torch.linalg.eigh(M / float(n))
+    gap, lam_max = float(lam[R] - lam[R - 1]), float(lam[-1])
+    if not gap > 64.0 * float(np.finfo(np.float64).eps) * lam_max:
+        raise ValueError(f"--score vim: the principal subspace of dimension D = {D} is not determined by these {n} training rows: "
+                         f"lambda_D = {float(lam[R]):.6e}, lambda_(D+1) = {float(lam[R - 1]):.6e}, lambda_max = {lam_max:.6e} "
+                         "(a training set of fewer than D rows, or a flat spectrum): choose another --vim-dim")
+    return vec[:, :R].T.contiguous().float(), lam
+
+
+def get_vim_fit(args, net, train_loader, test_labels):
+    """`--score vim` (Wang et al., CVPR 2022), the fit: {"bank", "K", "R", "D", "alpha", "T", "n", "eigenvalues"}.
+      * every rank encodes its `shard_range` of the training set and keeps its shard of unit-norm features on the device (they
+        are not gathered); their uncentred fp64 Gram matrix comes from the running sums of the Mahalanobis fit
+        (`net.maha_fit_accumulate`, no shift: the zero-shot head has no bias, ViM's origin is 0) and goes through one all-reduce
+        with n;
+      * `vim_null_space` runs on every rank on the same bits: D = `vim_principal_dim(P, args.vim_dim)`, R = P - D;
+      * bank [K + R, P] = the prompt bank, then the basis rows;
+      * alpha = sum_i max_k logit[i, k] / sum_i resid[i] over ALL training rows (not the paper's sample of them), from one
+        `net.vim_scores(..., alpha=0, return_parts=True)` pass over the shard, both sums in fp64 and all-reduced.  The score
+        kernel takes it as fp32.
+    A loader that cannot be sharded by index is refused under world_size > 1, as by `get_knn_bank`."""
+    import logging
+
+    import torch
+
+    if not hasattr(net, "vim_scores") or not hasattr(net, "maha_fit_accumulate"):
+        raise TypeError("get_vim_fit needs a net with vim_scores and maha_fit_accumulate (a NativeCLIP); there is no eager fallback")
+    T = float(getattr(args, "vim_T", 0.01))
+    n_total = len(train_loader.dataset)
+    with torch.no_grad():
+        state = net.maha_fit_state(None)
+        shard = []
+        for images, _labels in _shard_batches(train_loader, n_total, "vim"):
+            f = _unit_image_features(net, images).contiguous()
+            net.maha_fit_accumulate(f, state)
+            shard.append(f)
+        gram = state["gram"]
+        dev = gram.device
+        n_t = torch.tensor([float(state["n"])], dtype=torch.float64, device=dev)
+        for t in (gram, n_t):
+            mdist.all_reduce_sum(t)
+        n = int(round(float(n_t.cpu()[0])))
+        if n < 1:
+            raise ValueError("--score vim: the training set is empty")
+        P = int(gram.shape[0])
+        D = vim_principal_dim(P, getattr(args, "vim_dim", 0))
+        ns, lam = vim_null_space(gram, n, D)
+        prompts = prompt_bank(args, net, test_labels).float()
+        K, R = int(prompts.shape[0]), P - D
+        bank = torch.cat([prompts.to(dev), ns.to(dev)]).contiguous()
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)  # sum maxlogit, sum resid
+        for f in shard:
+            _, parts = net.vim_scores(f, bank, K, T=T, alpha=0.0, return_parts=True)
+            sums[0] += parts[:, 2].double().sum()
+            sums[1] += parts[:, 0].double().sum()
+        mdist.all_reduce_sum(sums)
+    top, res = (float(v) for v in sums.cpu())
+    alpha = top / res if res != 0.0 else float("nan")
+    if res == 0.0 or not np.isfinite(alpha):
+        raise ValueError(f"--score vim: alpha = sum max-logit / sum residual = {top} / {res} is not a finite number: the training "
+                         "features have no component outside the principal subspace (or are not finite)")
+    if alpha <= 0.0:
+        logging.getLogger(__name__).warning(
+            f"--score vim: alpha = {alpha:.6g} is not positive (sum max-logit = {top:.6g}): the residual enters the score with the "
+            "wrong sign; seeded synthetic weights can produce this, a trained checkpoint should not")
+    return {"bank": bank, "K": K, "R": R, "D": D, "alpha": alpha, "T": T, "n": n, "eigenvalues": lam.numpy()}
+
+
+def get_vim_score(args, net, loader, fit):
+    """`--score vim`: per sample alpha * resid - lse (`net.vim_scores` against `fit["bank"]` of `get_vim_fit`): the norm of its
+    unit-norm feature's component in the null space of the training features' principal subspace, scaled to logit units, minus
+    the energy of its logits at temperature fit["T"]; larger = more OOD.  Sharded and gathered like `get_knn_score`; EVERY
+    sample is scored.  Returns a float32 ndarray [len(loader.dataset)]."""
+    import torch
+
+    if not hasattr(net, "vim_scores"):
+        raise TypeError("get_vim_score needs a net with vim_scores (a NativeCLIP); there is no eager fallback")
+    bank, K = fit["bank"], int(fit["K"])
+    T, alpha = float(fit["T"]), float(fit["alpha"])
+    n_total = len(loader.dataset)
+    with torch.no_grad():
+        out = [net.vim_scores(_unit_image_features(net, images), bank, K, T=T, alpha=alpha)
+               for images, _labels in _shard_batches(loader, n_total, "vim")]
+    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
+
+
 def _gather_batch_shards(local, n_total, ws):
     """All-gather score shards whose sizes only the owning rank knows (batch-range split of a generic
     loader: the last batch may be short, batch sizes need not be uniform).  Counts are exchanged first;

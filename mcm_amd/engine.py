@@ -150,6 +150,9 @@ def load_library(harness: bool = False):
     L.mcm_knn_score_features.argtypes = [vp, vp, i32, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
     L.mcm_neglabel_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
     L.mcm_neglabel_score_features.argtypes = [vp, vp, i32, vp, i32, i32, i32, ctypes.c_float, i32, vp, ctypes.c_int64, vp, vp, vp]
+    L.mcm_vim_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
+    L.mcm_vim_score_features.argtypes = [vp, vp, i32, vp, i32, i32, vp, ctypes.c_float, ctypes.c_float, i32, vp, ctypes.c_int64,
+                                         vp, vp, vp]
     L.mcm_local_workspace_bytes.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
     L.mcm_local_score_features.argtypes = [vp, vp, i32, i32, vp, i32, ctypes.c_float, vp, ctypes.c_int64, vp, vp, vp]
     L.mcm_encode_image_local.argtypes = [vp, vp, i32, i32, vp, vp, vp]
@@ -183,6 +186,7 @@ EXPORTED_SYMBOLS = [
     "mcm_knn_workspace_bytes", "mcm_knn_score_features",
     "mcm_neglabel_workspace_bytes", "mcm_neglabel_score_features",
     "mcm_local_workspace_bytes", "mcm_local_score_features", "mcm_encode_image_local", "mcm_score_glmcm",
+    "mcm_vim_workspace_bytes", "mcm_vim_score_features",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -450,6 +454,56 @@ class NativeCLIP:
             raise ValueError(f"neglabel_scores: refused (rc={rc}) for B={B}, n_id={K}, groups={G}, group_size={gs}, T={T}, "
                              f"splits={splits}: B, n_id, group_size >= 1, 1 <= groups <= 1024, T > 0 and finite, "
                              "0 <= splits <= 32 and proj_dim % 4 == 0 are required")
+        self._check(rc)
+
+    def vim_scores(self, features, bank, n_id, T: float = 0.01, alpha: float = 1.0, off=None, splits: int = 0,
+                   return_parts: bool = False):
+        """features [B,P], bank [n_id + R, P] fp32 (device) → [B] fp32: the ViM score alpha * resid - lse, resid the norm of the
+        row's projections on the bank's last R rows (the null-space basis; minus `off` [R] fp64 where given), lse the
+        log-sum-exp at temperature T of its dot products with the first n_id rows (the prompts) (include/mcm.h
+        mcm_vim_score_features); larger = more OOD.  `splits`: 0 = the library's choice, n = the bank in exactly n ranges
+        (results agree across it to rounding, and are the same bits for a fixed value).  `return_parts=True`: (scores,
+        parts [B,3] = resid, lse, maxlogit).  The workspace is a buffer of this object that grows on demand; queries go through
+        in blocks of at most 4096 rows."""
+        import torch
+
+        f, bk = self._bank_operands(features, bank)
+        K, splits, T, alpha = int(n_id), int(splits), float(T), float(alpha)
+        R = int(bk.shape[0]) - K
+        if K < 1 or R < 1:
+            raise ValueError(f"vim_scores: the bank has {bk.shape[0]} rows, n_id = {K}: both n_id and the basis rows behind "
+                             "them must be at least 1")
+        o = None
+        if off is not None:
+            o = off.to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
+            if o.shape != (R,):
+                raise ValueError(f"vim_scores: off must hold R = {R} values, got {tuple(o.shape)}")
+        B = int(f.shape[0])
+        scores = torch.empty(B, device=self.device, dtype=torch.float32)
+        parts = torch.empty((B, 3), device=self.device, dtype=torch.float32) if return_parts else None
+        for s, n, work in self._bank_blocks(B, getattr(self, "_vim_work", None), lambda n, need: self._check_vim(
+                self._lib.mcm_vim_workspace_bytes(self._h, n, K, R, splits, need), n, K, R, T, alpha, splits)):
+            self._vim_work = work
+            self._check_vim(self._lib.mcm_vim_score_features(
+                self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, R, o.data_ptr() if o is not None else None, T, alpha,
+                splits, work.data_ptr(), work.numel() * 4, scores[s:s + n].data_ptr(),
+                parts[s:s + n].data_ptr() if return_parts else None, _stream_ptr()), n, K, R, T, alpha, splits)
+        return (scores, parts) if return_parts else scores
+
+    def _check_vim(self, rc, B, K, R, T, alpha, splits):
+        if rc == -1:
+            import math
+
+            bad = [what for what, wrong in (
+                (f"B={B} (B >= 1)", B < 1), (f"n_id={K} (n_id >= 1)", K < 1), (f"R={R} (R >= 1)", R < 1),
+                (f"n_id + R = {K + R} (at most 2^31 - 1)", K + R > 2 ** 31 - 1),
+                (f"T={T} (positive and finite)", not (T > 0 and math.isfinite(T))),
+                (f"alpha={alpha} (finite)", not math.isfinite(alpha)),
+                (f"splits={splits} (0 <= splits <= 32)", not 0 <= splits <= 32),
+                (f"proj_dim={self.geo.proj_dim} (proj_dim % 4 == 0)", self.geo.proj_dim % 4 != 0)) if wrong]
+            raise ValueError(f"vim_scores: refused (rc={rc}): " + ("; ".join(bad) if bad else
+                             f"B={B}, n_id={K}, R={R}, T={T}, alpha={alpha}, splits={splits}: "
+                             + self._lib.mcm_last_error(self._h).decode()))
         self._check(rc)
 
     # -- GL-MCM: the local (patch-level) term next to MCM (include/mcm.h mcm_score_glmcm; DESIGN.md 4.14) -------------------
