@@ -1,7 +1,12 @@
-// bank_sim.hpp — the bank walk of the bank-streamed scores (knn.hip, neglabel.hip): a workgroup of 256
-// threads takes 64 query rows and a range of bank rows and sees the exact-fp32 similarities 64 x 256 at a time in LDS,
-// without the [B, N] matrix ever existing in HBM.  A score is what its kernel does with a tile (the callback of walk)
-// and the state it keeps *behind* the tile: its dynamic LDS is TILE_BYTES plus what it states for itself.
+// bank_sim.hpp — what the bank-streamed scores share.
+// The walk (knn.hip, neglabel.hip, vim.hip, glmcm.hip): a workgroup of 256 threads takes 64 query rows and a range of bank
+// rows and sees the exact-fp32 similarities 64 x 256 at a time in LDS, without the [B, N] matrix ever existing in HBM.  A
+// score is what its kernel does with a tile (the callback of walk) and the state it keeps *behind* the tile: its dynamic
+// LDS is TILE_BYTES plus what it states for itself.
+// The fold (neglabel.hip, vim.hip, glmcm.hip; not knn.hip, which selects and sums nothing): the online log-sum-exp of tile
+// rows.  lse_fold takes columns of a tile row into a query's open pair (max, sum exp((s - max) / T)), the sum in fp64; the
+// open pairs of a workgroup's queries lie behind the tile (PAIR_BYTES, pair_sums, pair_maxima, pair_reset); lse_merge adds
+// the pairs that the splits of a bank left (neglabel.hip, vim.hip; glmcm.hip walks the whole bank in one workgroup).
 #pragma once
 #include "common.hpp"
 
@@ -108,6 +113,52 @@ __device__ __forceinline__ void walk(const float* feats, const float* bank, int 
     __syncthreads();
     tile(n0, ncols);
   }
+}
+
+// ---- the fold: an online log-sum-exp over tile rows ---------------------------------------------------------------------
+// The open pair of every query of the workgroup lies behind the tile: the sums [Q] fp64 at TILE_BYTES, then `own` fp64
+// arrays [Q] that a score keeps there for itself (vim.hip's sums of squares), then the maxima [Q] fp32.
+constexpr int PAIR_BYTES = Q * (int)(sizeof(double) + sizeof(float));
+static_assert(TILE_BYTES % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
+__device__ __forceinline__ double* pair_sums(float* lds) { return (double*)(lds + SIM_FLOATS); }
+__device__ __forceinline__ float* pair_maxima(double* last) { return (float*)(last + Q); }  // last: the fp64 array before them
+// Thread tid < Q empties pair tid, and entry tid of the score's `own` arrays with it; the kernel's barrier follows.  The
+// `if (tid < Q)` stands at the call, in the kernel: with the branch in here the kernels' q0 / nq arithmetic was placed
+// on the other side of it and the three kernels came out with other instructions.
+template <class... Own>
+__device__ __forceinline__ void pair_reset(int tid, double* st_sum, float* st_max, Own*... own) {
+  st_sum[tid] = 0.0;
+  ((own[tid] = 0.0), ...);
+  st_max[tid] = -INFINITY;
+}
+
+// One wave folds columns [c, ce) of a tile row into the open pair (m, sum): sum becomes sum exp((s - m) / T) over the
+// columns folded so far at their maximum m.  Every lane ends with the same m and sum.
+__device__ __forceinline__ void lse_fold(const float* row, int c, int ce, int lane, double inv_t, float& m, double& sum) {
+  float mx = -INFINITY;
+  for (int i = c + lane; i < ce; i += 64) mx = fmaxf(mx, row[i]);  // a NaN is skipped here and poisons the sum below
+  const float M = fmaxf(m, wave_max(mx));
+  double part = 0.0;
+  for (int i = c + lane; i < ce; i += 64) part += exp(((double)row[i] - (double)M) * inv_t);
+  part = wave_sum(part);
+  if (m != M) sum *= exp(((double)m - (double)M) * inv_t);  // m = -inf: the sum is 0 and stays 0
+  sum += part;
+  m = M;
+}
+
+// The pairs of splits s0 .. s1 (pair(s) = float2{max, sum}, the sum as fp32 as a split stores it) merged: M their largest
+// maximum, the return value sum_s sum(s) exp((max(s) - M) / T) in fp64, added in split order.  The log-sum-exp of the rows
+// behind them is M / T + log of it.
+template <class Pair>
+__device__ __forceinline__ double lse_merge(int s0, int s1, double inv_t, float& M, Pair&& pair) {
+  M = -INFINITY;
+  for (int s = s0; s <= s1; ++s) M = fmaxf(M, pair(s).x);
+  double tot = 0.0;
+  for (int s = s0; s <= s1; ++s) {
+    const float2 v = pair(s);
+    tot += v.x == M ? (double)v.y : (double)v.y * exp(((double)v.x - (double)M) * inv_t);
+  }
+  return tot;
 }
 
 // raises a kernel's dynamic-LDS limit on the current device, once per device (`done`: a static of the launcher)

@@ -4,8 +4,9 @@
 // prompts its bank; images do not align with the walk's 64-query tiles, so the per-image maximum is a launch of its own.
 //   glm_rows_kernel    grid (query tiles of 64 rows of [B R, P]).  A workgroup walks the whole bank (bank_sim.hpp: the
 //                      64 x 256 exact-fp32 similarities of a tile in LDS, the s[b, n] that knn.hip and neglabel.hip see);
-//                      a wave per query folds every tile into the row's online-softmax pair (max, sum exp((s - max) / T)),
-//                      the sum in fp64.  At the end row[q] = (float)(1 / sum): the softmax's largest probability.
+//                      a wave per query folds every tile into the row's open pair (bank_sim::lse_fold: max,
+//                      sum exp((s - max) / T) in fp64).  At the end row[q] = (float)(1 / sum): the softmax's largest
+//                      probability.
 //   glm_image_kernel   one workgroup per image: the maximum of its R row values, NaN if any of them is NaN.
 // Nothing is combined across workgroups by atomics, no workgroup waits for another, every loop is bounded by the
 // arguments; every row's value is one fixed computation wherever the row falls, and a maximum has no order.
@@ -20,9 +21,7 @@ namespace {
 
 namespace glm {
 using namespace bank_sim;
-// behind the tile: the open pair of every query, sum [Q] fp64 then max [Q] fp32
-constexpr int LDS_BYTES = TILE_BYTES + Q * (int)(sizeof(double) + sizeof(float));
-static_assert(TILE_BYTES % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
+constexpr int LDS_BYTES = TILE_BYTES + PAIR_BYTES;  // behind the tile: the open pair of every query
 constexpr int IMG_THREADS = 256;
 }  // namespace glm
 
@@ -35,33 +34,17 @@ struct GlmArgs {
   int M, P, K;
 };
 
-__device__ __forceinline__ float glm_wave_max(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
-  return x;
-}
-
-// the butterfly adds the same two values on both sides of every exchange, so every lane ends with the same bits
-__device__ __forceinline__ double glm_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 __global__ __launch_bounds__(glm::THREADS) void glm_rows_kernel(GlmArgs a) {
   using namespace glm;
   extern __shared__ __attribute__((aligned(16))) float glm_lds[];
-  double* st_sum = (double*)(glm_lds + SIM_FLOATS);
-  float* st_max = (float*)(st_sum + Q);
+  double* st_sum = pair_sums(glm_lds);
+  float* st_max = pair_maxima(st_sum);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int q0 = blockIdx.x * Q;  // M <= INT_MAX
   const int nq = a.M - q0 < Q ? a.M - q0 : Q;
 
-  if (tid < Q) {
-    st_sum[tid] = 0.0;
-    st_max[tid] = -INFINITY;
-  }
+  if (tid < Q) pair_reset(tid, st_sum, st_max);
   __syncthreads();
 
   // either zero gives the same bits in everything below: the tile is taken as the MFMA left it
@@ -70,18 +53,11 @@ __global__ __launch_bounds__(glm::THREADS) void glm_rows_kernel(GlmArgs a) {
       const int q = w * (Q / 4) + qi;
       if (q >= nq) break;
       const float* row = glm_lds + q * LDSIM;
-      const float m = st_max[q];
+      float m = st_max[q];
       double sum = st_sum[q];
-      float mx = -INFINITY;
-      for (int i = lane; i < ncols; i += 64) mx = fmaxf(mx, row[i]);  // a NaN is skipped here and poisons the sum below
-      const float M = fmaxf(m, glm_wave_max(mx));
-      double part = 0.0;
-      for (int i = lane; i < ncols; i += 64) part += exp(((double)row[i] - (double)M) * a.inv_t);
-      part = glm_wave_sum(part);
-      if (m != M) sum *= exp(((double)m - (double)M) * a.inv_t);  // m = -inf: the sum is 0 and stays 0
-      sum += part;
+      lse_fold(row, 0, ncols, lane, a.inv_t, m, sum);
       if (lane == 0) {
-        st_max[q] = M;
+        st_max[q] = m;
         st_sum[q] = sum;
       }
     }

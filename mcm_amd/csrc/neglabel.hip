@@ -5,10 +5,11 @@
 //   neg_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows (bank_sim.hpp: the
 //                       64 x 256 exact-fp32 similarities of a tile in LDS, the s[b, n] that knn.hip sees).  A tile is cut
 //                       into segments (a range intersected with the tile); a wave per query folds every segment into
-//                       the open online-softmax pair (max, sum exp((s - max) / T)) of its range, the sum in fp64.  The
+//                       the open pair of its range (bank_sim::lse_fold: max, sum exp((s - max) / T) in fp64).  The
 //                       pair is written to work[split, query, range] when its range or the split ends.
-//   neg_combine_kernel  one workgroup per query: per range the partial pairs of the splits that hold rows of it, in split
-//                       order, give its log-sum-exp in fp64; S[g] = 1 / (1 + exp(LN[g] - LI)); the mean is a fixed tree.
+//   neg_combine_kernel  one workgroup per query: per range the partial pairs of the splits that hold rows of it, merged
+//                       in split order (bank_sim::lse_merge), give its log-sum-exp in fp64;
+//                       S[g] = 1 / (1 + exp(LN[g] - LI)); the mean is a fixed tree.
 // Which (split, range) slots were written follows from K, gs and the split length alone, and the second launch reads
 // exactly those: nothing is pre-filled and no unwritten word of the workspace is read.  Nothing is summed across
 // workgroups by atomics, no workgroup waits for another, every loop is bounded by the arguments.
@@ -21,9 +22,7 @@ namespace {
 
 namespace neg {
 using namespace bank_sim;
-// behind the tile: the open pair of every query, sum [Q] fp64 then max [Q] fp32
-constexpr int LDS_BYTES = TILE_BYTES + Q * (int)(sizeof(double) + sizeof(float));
-static_assert(TILE_BYTES % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
+constexpr int LDS_BYTES = TILE_BYTES + PAIR_BYTES;  // behind the tile: the open pair of every query
 }  // namespace neg
 
 struct NegArgs {
@@ -35,24 +34,11 @@ struct NegArgs {
   int B, P, K, G, gs;
 };
 
-__device__ __forceinline__ float neg_wave_max(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
-  return x;
-}
-
-// the butterfly adds the same two values on both sides of every exchange, so every lane ends with the same bits
-__device__ __forceinline__ double neg_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
   using namespace neg;
   extern __shared__ __attribute__((aligned(16))) float neg_lds[];
-  double* st_sum = (double*)(neg_lds + SIM_FLOATS);
-  float* st_max = (float*)(st_sum + Q);
+  double* st_sum = pair_sums(neg_lds);
+  float* st_max = pair_maxima(st_sum);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int q0 = blockIdx.x * Q;
@@ -61,10 +47,7 @@ __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
   int64_t lo, hi;
   split_bounds(s, a.per, a.N, lo, hi);
 
-  if (tid < Q) {
-    st_sum[tid] = 0.0;
-    st_max[tid] = -INFINITY;
-  }
+  if (tid < Q) pair_reset(tid, st_sum, st_max);
   __syncthreads();
 
   // either zero gives the same bits in everything below: the tile is taken as the MFMA left it
@@ -82,15 +65,7 @@ __global__ __launch_bounds__(neg::THREADS) void neg_partial_kernel(NegArgs a) {
         const int rg = n < a.K ? 0 : 1 + (n - a.K) / a.gs;
         const int rend = rg == 0 ? a.K : a.K + rg * a.gs;  // <= N
         const int ce = rend < tile_end ? rend - n0 : ncols;
-        float mx = -INFINITY;
-        for (int i = c + lane; i < ce; i += 64) mx = fmaxf(mx, row[i]);  // a NaN is skipped here and poisons the sum below
-        const float M = fmaxf(m, neg_wave_max(mx));
-        double part = 0.0;
-        for (int i = c + lane; i < ce; i += 64) part += exp(((double)row[i] - (double)M) * a.inv_t);
-        part = neg_wave_sum(part);
-        if (m != M) sum *= exp(((double)m - (double)M) * a.inv_t);  // m = -inf: the sum is 0 and stays 0
-        sum += part;
-        m = M;
+        lse_fold(row, c, ce, lane, a.inv_t, m, sum);
         if (rend <= tile_end || tile_end == hi) {  // the range or the split ends here: the pair is complete
           if (lane == 0) a.work[((int64_t)s * a.B + q0 + q) * (int64_t)(a.G + 1) + rg] = float2{m, (float)sum};
           m = -INFINITY;
@@ -120,13 +95,8 @@ __device__ __forceinline__ double neg_range_lse(const NegCombineArgs& a, int64_t
   const int s0 = lo / a.per, s1 = (hi - 1) / a.per;  // s1 < S: hi <= N <= S per
   const int64_t stride = (int64_t)a.B * (a.G + 1);
   const float2* p = a.work + b * (int64_t)(a.G + 1) + rg;
-  float M = -INFINITY;
-  for (int s = s0; s <= s1; ++s) M = fmaxf(M, p[s * stride].x);
-  double tot = 0.0;
-  for (int s = s0; s <= s1; ++s) {
-    const float2 v = p[s * stride];
-    tot += v.x == M ? (double)v.y : (double)v.y * exp(((double)v.x - (double)M) * a.inv_t);
-  }
+  float M;
+  const double tot = bank_sim::lse_merge(s0, s1, a.inv_t, M, [=](int s) { return p[s * stride]; });
   return (double)M * a.inv_t + log(tot);
 }
 

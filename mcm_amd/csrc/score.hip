@@ -23,17 +23,11 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 constexpr int NWV = 16;  // waves per workgroup: the per-prompt dot products are a dependent
                          // load -> fma -> cross-lane chain, so more waves = shorter chain
 
 __device__ __forceinline__ double block_sum_d(double v, double* red, int lane, int wave) {
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   __syncthreads();
   if (lane == 0) red[wave] = v;
   __syncthreads();
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(256) void maha_prepare_kernel(const float* __restri
     w[(size_t)c * P + p] = a + b;
     kc += mu[p] * a;
   }
-  kc = wave_sum_d(kc);
+  kc = wave_sum(kc);
   if ((tid & 63) == 0) red[tid >> 6] = kc;
   __syncthreads();
   if (tid == 0) k[c] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -235,7 +229,7 @@ __global__ __launch_bounds__(NWV * 64) void maha_score_kernel(const float* __res
   for (int p = wave; p < P; p += NWV) {
     double a = 0.0;
     for (int j = lane; j < P; j += 64) a += (double)prec[(size_t)p * P + j] * f[j];
-    a = wave_sum_d(a);
+    a = wave_sum(a);
     if (lane == 0) qa += f[p] * a;
   }
   const double q = block_sum_d(lane == 0 ? qa : 0.0, red, lane, wave);
@@ -243,7 +237,7 @@ __global__ __launch_bounds__(NWV * 64) void maha_score_kernel(const float* __res
   for (int c = wave; c < C; c += NWV) {
     double a = 0.0;
     for (int j = lane; j < P; j += 64) a += w[(size_t)c * P + j] * f[j];
-    a = wave_sum_d(a);
+    a = wave_sum(a);
     best = fmin(best, q - a + k[c]);
   }
   __syncthreads();

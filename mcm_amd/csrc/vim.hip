@@ -5,12 +5,12 @@
 //   vim_partial_kernel  grid (query tiles of 64) x (bank splits).  A workgroup walks its split's rows (bank_sim.hpp: the
 //                       64 x 256 exact-fp32 similarities of a tile in LDS, the s[b, n] that knn.hip sees).  A tile is cut
 //                       at row K into at most two segments; a wave per query folds the prompt segment into the open
-//                       online-softmax pair (max, sum exp((s - max) / T)), the sum in fp64, and adds the basis
-//                       segment's (s - off)^2 to an fp64 sum of squares.  When the split ends the query's slot
+//                       pair (bank_sim::lse_fold: max, sum exp((s - max) / T) in fp64) and adds the basis segment's
+//                       (s - off)^2 to an fp64 sum of squares.  When the split ends the query's slot
 //                       work[split, query] = {max, (float) sum, ssq} is written.
-//   vim_combine_kernel  one thread per query: the log-sum-exp from the slots of the splits that hold prompt rows, the sum
-//                       of squares from the slots of the splits that hold basis rows, both in split order in fp64; then
-//                       the square root and the score.
+//   vim_combine_kernel  one thread per query: the log-sum-exp from the slots of the splits that hold prompt rows
+//                       (bank_sim::lse_merge), the sum of squares from the slots of the splits that hold basis rows, both
+//                       in split order in fp64; then the square root and the score.
 // Which slots were written follows from K, R and the split length alone (a split that holds a row writes every query's
 // slot), and the second launch reads exactly those: nothing is pre-filled and no unwritten word of the workspace is
 // read.  Nothing is summed across workgroups by atomics, no workgroup waits for another, every loop is bounded by the
@@ -24,9 +24,8 @@ namespace {
 
 namespace vim {
 using namespace bank_sim;
-// behind the tile: the open state of every query, sum [Q] fp64, ssq [Q] fp64, then max [Q] fp32
-constexpr int LDS_BYTES = TILE_BYTES + Q * (int)(2 * sizeof(double) + sizeof(float));
-static_assert(TILE_BYTES % sizeof(double) == 0, "the fp64 sums must be 8-byte aligned");
+// behind the tile: the open pair of every query with this score's own ssq [Q] fp64 between its sums and its maxima
+constexpr int LDS_BYTES = TILE_BYTES + PAIR_BYTES + Q * (int)sizeof(double);
 }  // namespace vim
 
 // what a split knows of a query: the pair of its prompt rows and the sum of squares of its basis rows
@@ -47,25 +46,12 @@ struct VimArgs {
   int B, P, K;
 };
 
-__device__ __forceinline__ float vim_wave_max(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
-  return x;
-}
-
-// the butterfly adds the same two values on both sides of every exchange, so every lane ends with the same bits
-__device__ __forceinline__ double vim_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 __global__ __launch_bounds__(vim::THREADS) void vim_partial_kernel(VimArgs a) {
   using namespace vim;
   extern __shared__ __attribute__((aligned(16))) float vim_lds[];
-  double* st_sum = (double*)(vim_lds + SIM_FLOATS);
+  double* st_sum = pair_sums(vim_lds);
   double* st_ssq = st_sum + Q;
-  float* st_max = (float*)(st_ssq + Q);
+  float* st_max = pair_maxima(st_ssq);
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int q0 = blockIdx.x * Q;
@@ -74,11 +60,7 @@ __global__ __launch_bounds__(vim::THREADS) void vim_partial_kernel(VimArgs a) {
   int64_t lo, hi;
   split_bounds(s, a.per, a.N, lo, hi);
 
-  if (tid < Q) {
-    st_sum[tid] = 0.0;
-    st_ssq[tid] = 0.0;
-    st_max[tid] = -INFINITY;
-  }
+  if (tid < Q) pair_reset(tid, st_sum, st_max, st_ssq);
   __syncthreads();
 
   // either zero gives the same bits in everything below: the tile is taken as the MFMA left it
@@ -91,17 +73,7 @@ __global__ __launch_bounds__(vim::THREADS) void vim_partial_kernel(VimArgs a) {
       const float* row = vim_lds + q * LDSIM;
       float m = st_max[q];
       double sum = st_sum[q], ssq = st_ssq[q];
-      if (cut > 0) {
-        float mx = -INFINITY;
-        for (int i = lane; i < cut; i += 64) mx = fmaxf(mx, row[i]);  // a NaN is skipped here and poisons the sum below
-        const float M = fmaxf(m, vim_wave_max(mx));
-        double part = 0.0;
-        for (int i = lane; i < cut; i += 64) part += exp(((double)row[i] - (double)M) * a.inv_t);
-        part = vim_wave_sum(part);
-        if (m != M) sum *= exp(((double)m - (double)M) * a.inv_t);  // m = -inf: the sum is 0 and stays 0
-        sum += part;
-        m = M;
-      }
+      if (cut > 0) lse_fold(row, 0, cut, lane, a.inv_t, m, sum);
       if (cut < ncols) {
         const int j0 = n0 - a.K;  // off[j] belongs to bank row K + j = n0 + i: j = j0 + i in [0, R)
         double part = 0.0;
@@ -109,7 +81,7 @@ __global__ __launch_bounds__(vim::THREADS) void vim_partial_kernel(VimArgs a) {
           const double d = a.off ? (double)row[i] - a.off[j0 + i] : (double)row[i];
           part = fma(d, d, part);
         }
-        ssq += vim_wave_sum(part);
+        ssq += wave_sum(part);
       }
       if (lane == 0) {
         if (tile_end == hi) {  // the split ends here: the slot is complete
@@ -143,13 +115,12 @@ __global__ __launch_bounds__(vim::THREADS) void vim_combine_kernel(VimCombineArg
   // the splits that hold a prompt row are 0 .. (K - 1) / per, the ones that hold a basis row K / per .. (N - 1) / per:
   // exactly the slots vim_partial_kernel wrote ((N - 1) / per < S: N <= S per)
   const int p1 = (a.K - 1) / a.per, r0 = a.K / a.per, r1 = (a.N - 1) / a.per;
-  float M = -INFINITY;
-  for (int s = 0; s <= p1; ++s) M = fmaxf(M, p[(int64_t)s * a.B].m);
-  double tot = 0.0;
-  for (int s = 0; s <= p1; ++s) {
-    const VimSlot v = p[(int64_t)s * a.B];
-    tot += v.m == M ? (double)v.sum : (double)v.sum * exp(((double)v.m - (double)M) * a.inv_t);
-  }
+  const int64_t stride = a.B;
+  float M;
+  const double tot = bank_sim::lse_merge(0, p1, a.inv_t, M, [=](int s) {
+    const VimSlot v = p[s * stride];
+    return float2{v.m, v.sum};
+  });
   const double maxlogit = (double)M * a.inv_t;
   const double lse = maxlogit + log(tot);
   double ssq = 0.0;

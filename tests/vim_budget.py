@@ -32,8 +32,8 @@ Arithmetic term.
     (R / 256 + 43) u relatively.  (A bound of one u per addition of non-negative terms holds for any association.)
     sqrt halves a relative error and rounds once:          A_resid = resid ((R / 256 + 43) / 2 + 2) u,
     taken times (1 + 2^-20) for the second-order terms;
-  * lse: the pair (max, sum) per split and their combination are neglabel.hip's, statement for statement, with one range of
-    len = K rows: tests/neglabel_budget.py derives dL(len, X), X = 2 max_k |s[b, k]| / Td, for it (steps (a) - (f) there, the
+  * lse: the pair (max, sum) per split and their combination are neglabel.hip's — the same functions, bank_sim::lse_fold /
+    lse_merge — with one range of len = K rows: tests/neglabel_budget.py derives dL(len, X), X = 2 max_k |s[b, k]| / Td, for it (steps (a) - (f) there, the
     fp32 rounding of the stored sum included), and that function is used here as it stands:   A_lse = dL(K, X);
   * maxlogit = fl((double) M * fl(1 / Td)): two roundings of a value of at most X / 2:   A_max = 2 u |maxlogit|;
   * score = fl(fl(a resid') - lse'): |a| (E_resid + A_resid) + E_lse + A_lse + u (|a resid| + |score|), then rounded to fp32.
