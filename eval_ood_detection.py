@@ -1,6 +1,6 @@
 """eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
 and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`, `--neg-*`).
+`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`, `--neg-*`, `--ctx*`).
 
 Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
 set) → AUROC / AUPR / FPR95 → log + CSV.
@@ -143,7 +143,30 @@ def process_args(argv=None):
                         "1..proj_dim - 1; 0 (default) = proj_dim // 2 below 768, 512 for 768 <= proj_dim < 2048, 1000 above.  The "
                         "training set is the \"train\" set (--subset / --max_count as for --score knn), every rank fitting its shard")
     p.add_argument("--vim-T", default=0.01, type=float, help="--score vim: the temperature of the logits (--T is ignored there)")
+    p.add_argument("--ctx", default=None, metavar="FILE",
+                   help="learned prompt contexts (CoOp, Zhou et al. 2022; LoCoOp, Miyai et al. 2023): the prompt bank of every "
+                        "concept-matching score is CoOp's \"X X ... X classname.\" with the n_ctx context vectors of FILE in place "
+                        "of the X — a CoOp / LoCoOp checkpoint (prompt_learner/model.pth.tar-N: state_dict['ctx'], shared "
+                        "[n_ctx, width] or per class [K, n_ctx, width]), a state dict with 'ctx', or a .npy of the array.  Not with "
+                        "--templates or --score maha / knn / neglabel")
+    p.add_argument("--ctx-position", default="end", choices=["end", "middle", "front"],
+                   help="--ctx: where the class name sits among the context vectors (CoOp's CLASS_TOKEN_POSITION)")
+    p.add_argument("--ctx-T", default=0.01, type=float,
+                   help="--ctx: the temperature of the MCM-family and GL-MCM scores (--T is ignored there: the contexts were "
+                        "trained through softmax(100 cos), and --T is an int by the reference's contract)")
     args = p.parse_args(argv)
+    if args.ctx:
+        if args.templates:
+            p.error("--ctx and --templates exclude each other (a learned context replaces the template's words)")
+        if args.score in ("maha", "knn"):
+            p.error(f"--ctx needs a score with a prompt bank: --score {args.score} has none")
+        if args.score == "neglabel":
+            p.error("--ctx is not available with --score neglabel (its mined negatives are template prompts and would sit in another "
+                    "space than the ID rows)")
+        if not (args.ctx_T > 0.0 and np.isfinite(args.ctx_T)):
+            p.error("--ctx-T must be positive and finite")
+        if args.score != "vim":  # (vim's logits keep --vim-T)
+            args.T = args.ctx_T
     if args.score == "GL-MCM":
         if not np.isfinite(args.gl_lambda):
             p.error("--gl-lambda must be finite")
@@ -339,6 +362,18 @@ def main(argv=None):
     if args.dtype == "bf16":
         log.debug("NOTE: bf16 operands do not hold the reference's AUROC / FPR95 to 1e-4 (measured 1e-4 ... 1e-3 against "
                   "HF fp32, DESIGN.md section 2.1); --dtype fp16 (the default) does")
+    if args.ctx:
+        from mcm_amd.prompts import load_context
+
+        try:
+            c = load_context(args.ctx)
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"--ctx: {e}")
+        if c.ctx.shape[-1] != net.geo.t_width:
+            raise SystemExit(f"--ctx {args.ctx}: context vectors are {c.ctx.shape[-1]} wide, the text tower of {args.CLIP_ckpt} {net.geo.t_width}")
+        log.debug(f"--ctx {args.ctx}: n_ctx = {c.n_ctx}, {'per-class (' + str(c.ctx.shape[0]) + ' classes)' if c.per_class else 'shared'} "
+                  f"context, class name at the {args.ctx_position}"
+                  + (f"; --T is ignored, the temperature is --ctx-T {args.ctx_T}" if args.score != "vim" else ""))
     args.ckpt = HUB_IDS[args.CLIP_ckpt]  # reference utils/train_eval_util.py:19-22 (ckpt_mapping)
     if args.in_dataset == "ImageNet10":
         out_datasets = ["ImageNet20"]

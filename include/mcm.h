@@ -46,7 +46,8 @@ extern "C" {
                           * (still 5) mcm_neglabel_workspace_bytes / mcm_neglabel_score_features: two added symbols, on the same terms
                           * (still 5) mcm_local_workspace_bytes / mcm_local_score_features / mcm_encode_image_local /
                           * mcm_score_glmcm: four added symbols, on the same terms
-                          * (still 5) mcm_vim_workspace_bytes / mcm_vim_score_features: two added symbols, on the same terms */
+                          * (still 5) mcm_vim_workspace_bytes / mcm_vim_score_features: two added symbols, on the same terms
+                          * (still 5) mcm_encode_text_ctx: an added symbol, on the same terms */
 
 /* error codes */
 #define MCM_OK 0
@@ -185,6 +186,25 @@ int mcm_encode_image_ex(mcm_handle* h, const void* pixels_dev, int32_t pixel_for
                         int32_t normalize, float* out_dev, void* stream);
 int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S, int32_t normalize,
                        float* out_dev, void* stream);
+
+/* Learned prompt contexts.  Replaces CoOp's `PromptLearner.forward` + `TextEncoder.forward` (Zhou et al., "Learning to Prompt
+ * for Vision-Language Models"; LoCoOp trains the same module): token-embed the tokenised prompt "X X ... X classname.",
+ * overwrite the n_ctx placeholder positions with the learned vectors, add the position embedding, run the unchanged
+ * transformer, ln_final, pool at `tokenized_prompts.argmax(-1)`, project.  It is mcm_encode_text_ex with the embedding step
+ * replaced — the same passes of max_prompt_tokens / S prompts, the same layers, the same pooling kernel:
+ *   x[k, s] = (slot[k, s] < 0 ? token_embedding[ids[k, s]] : ctx[set(k), slot[k, s]]) + position_embedding[s]
+ * ids_host / slot_host: int32 [K,S] row-major, host memory.  slot -1 = an ordinary token; slot j in [0, n_ctx) = row j of the
+ * prompt's context set.  The id under a context slot is a placeholder (CoOp's "X"): it is not looked up, but it takes part in
+ * pooling like any id — the pooled row is the first position of the largest id of ids_host — and must be a valid id.
+ * ctx_dev: fp32 [n_sets, n_ctx, t_width], device memory, 16-byte aligned; set(k) = 0 when n_sets == 1 (CoOp's unified
+ * context), k when n_sets == K (class-specific contexts, "CSC").  It is read on `stream`: the caller keeps it alive until the
+ * stream has passed the call.  Nothing is allocated: the slot map travels in the id words a pass uploads anyway.
+ * out_dev: fp32 [K, proj_dim]; normalize as mcm_encode_text_ex.
+ * MCM_EINVAL, with nothing launched: a NULL ids_host / slot_host / ctx_dev / out_dev; K, S or n_ctx < 1; n_sets other than 1 or K;
+ * a slot outside -1 ... n_ctx - 1; an id outside the vocabulary; ctx_dev not 16-byte aligned.  MCM_ERANGE: S > max_positions. */
+int mcm_encode_text_ctx(mcm_handle* h, const int32_t* ids_host /* [K,S] */, const int32_t* slot_host /* [K,S] */,
+                        int32_t K, int32_t S, const float* ctx_dev /* [n_sets, n_ctx, t_width] fp32 */,
+                        int32_t n_ctx, int32_t n_sets, int32_t normalize, float* out_dev, void* stream);
 
 /* Replaces the scoring tail utils/detection_util.py:232-248 on already-normalised
  * features: sim = img @ text.T, softmax(sim/T), reduction `kind` → scores_dev fp32 [B].
@@ -713,6 +733,13 @@ int mcm_debug_op_pool_project(mcm_handle* h, const float* x_dev, int64_t x_rows,
  * Synchronises the stream. */
 int mcm_debug_op_text_embed(mcm_handle* h, const int32_t* ids_host, int32_t vocab, const float* tok_dev, const float* pos_dev,
                             float* x_dev, int32_t K, int32_t S, int32_t D, void* stream);
+/* The context form of the text embedding kernel on the caller's buffers: x [K * S, D] = (slot < 0 ? tok[ids[k * S + s]] :
+ * ctx[set, slot]) + pos[s]; ctx [n_sets, n_ctx, D] fp32 on the device, n_sets 1 (set 0 for every k) or K (set k).  Ids and slots are
+ * host memory and are checked.  MCM_EINVAL for D % 4 != 0, an id outside the table, a slot outside -1 ... n_ctx - 1, n_sets other
+ * than 1 or K, or a ctx_dev that is not 16-byte aligned.  Synchronises the stream. */
+int mcm_debug_op_text_embed_ctx(mcm_handle* h, const int32_t* ids_host, const int32_t* slot_host, int32_t vocab,
+                                const float* tok_dev, const float* pos_dev, const float* ctx_dev, int32_t n_ctx, int32_t n_sets,
+                                float* x_dev, int32_t K, int32_t S, int32_t D, void* stream);
 /* A/B and ablation bits of the GEMM kernels (gemm.hip, GemmArgs::dbg; 0 = shipped behaviour). */
 int mcm_debug_gemm_dbg(int32_t bits);
 /* A/B: run the QKV projection + attention of every layer per chunk of the batch (n chunks; 1 = shipped). */

@@ -405,6 +405,10 @@ hipError_t launch_patchify_u8(int prec, const uint8_t* pixels, void* patches, in
 hipError_t launch_bank_reduce(const float* feats, int K, int T, int P, float* bank, hipStream_t s);
 hipError_t launch_text_embed(const int32_t* ids, const float* tok, const float* pos, float* x,
                              int K, int S, int D, hipStream_t s);
+// launch_text_embed with a row source per position: a word >= 0 is a token id, a word w < 0 row -w - 1 of the prompt's context
+// set in ctx [n_sets, n_ctx, D] fp32 (16-byte aligned); the set is 0 when n_sets == 1, else k0 + k (k0: words' first prompt)
+hipError_t launch_text_embed_ctx(const int32_t* words, const float* tok, const float* pos, const float* ctx, float* x,
+                                 int K, int S, int D, int n_ctx, int n_sets, int k0, hipStream_t s);
 hipError_t launch_cvt_weight(int prec, const float* src, void* dst, int rows, int cols,
                              int cols_pad, hipStream_t s);
 // split form (16-bit modes): dst [rows, 2 * cols_pad], per 64-element K-step hi[64] then lo[64] with

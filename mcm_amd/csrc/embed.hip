@@ -140,6 +140,27 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restri
   }
 }
 
+// text_embed_kernel with a row source per position (learned prompt contexts, CoOp's PromptLearner.forward): a word w >= 0 of
+// `words` is a token id as above; w < 0 names row -w - 1 of the prompt's context set, ctx [n_sets, n_ctx, D] fp32 — set 0 for
+// every prompt when n_sets == 1, set k0 + k (k0 = the index of this pass's first prompt in the whole call) otherwise.  The row
+// choice is uniform over the workgroup; the add is text_embed_kernel's own, so a position holding a token id gets its bits.
+__global__ __launch_bounds__(256) void text_embed_ctx_kernel(const int32_t* __restrict__ words,
+                                                             const float* __restrict__ tok,
+                                                             const float* __restrict__ pos,
+                                                             const float* __restrict__ ctx, float* x,
+                                                             int K, int S, int D, int n_ctx, int n_sets, int k0) {
+  const int row = blockIdx.x;  // k*S + s
+  const int s = row % S;
+  const int w = words[row];
+  const size_t set = n_sets == 1 ? 0 : (size_t)(k0 + row / S);
+  const float* src = w >= 0 ? tok + (size_t)w * D : ctx + (set * n_ctx + (size_t)(-w - 1)) * D;
+  for (int d = threadIdx.x * 4; d < D; d += 1024) {
+    const float4 a = *(const float4*)(src + d);
+    const float4 p = *(const float4*)(pos + (size_t)s * D + d);
+    *(float4*)(x + (size_t)row * D + d) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+  }
+}
+
 template <int OUT>
 __global__ __launch_bounds__(256) void cvt_weight_kernel(const float* __restrict__ src, void* dst,
                                                          int rows, int cols, int cols_pad) {
@@ -346,6 +367,16 @@ hipError_t launch_text_embed(const int32_t* ids, const float* tok, const float* 
                              int K, int S, int D, hipStream_t s) {
   if (D % 4) return hipErrorInvalidValue;
   hipLaunchKernelGGL(text_embed_kernel, dim3(K * S), dim3(256), 0, s, ids, tok, pos, x, K, S, D);
+  return hipGetLastError();
+}
+
+// words: token id, or -(j + 1) for row j of the prompt's context set (the caller has checked ids < vocab and j < n_ctx);
+// k0: the index of words' first prompt in the whole call, which is its context set when n_sets != 1
+hipError_t launch_text_embed_ctx(const int32_t* words, const float* tok, const float* pos, const float* ctx, float* x,
+                                 int K, int S, int D, int n_ctx, int n_sets, int k0, hipStream_t s) {
+  if (D % 4 || K <= 0 || S <= 0 || n_ctx <= 0 || n_sets <= 0 || k0 < 0 || ((uintptr_t)ctx & 15)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(text_embed_ctx_kernel, dim3(K * S), dim3(256), 0, s, words, tok, pos, ctx, x, K, S, D, n_ctx,
+                     n_sets, k0);
   return hipGetLastError();
 }
 

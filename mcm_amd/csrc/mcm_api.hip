@@ -1271,18 +1271,16 @@ int mcm_encode_text(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S
   return mcm_encode_text_ex(h, ids_host, K, S, 1, out_dev, stream);
 }
 
-int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S, int32_t normalize,
-                       float* out_dev, void* stream) {
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (!ids_host || !out_dev) return fail(h, MCM_EINVAL, "null pointer");
+namespace {
+// The text tower over validated prompts, in passes of max_prompt_tokens / S prompts.  slot_host == NULL: mcm_encode_text_ex, the
+// ids embedded by launch_text_embed as they always were.  Otherwise mcm_encode_text_ctx: the slot map travels in the id words
+// the pass uploads anyway — a position with slot j >= 0 is staged as -(j + 1), which launch_text_embed_ctx reads as row j of the
+// prompt's context set — so there is no buffer beyond mcm_encode_text_ex's.  Pooling reads ids_host either way, the placeholder
+// ids under the slots included.
+int encode_text_passes(mcm_handle* h, const int32_t* ids_host, const int32_t* slot_host, int32_t K, int32_t S,
+                       const float* ctx_dev, int32_t n_ctx, int32_t n_sets, int32_t normalize, float* out_dev, hipStream_t s) {
   const mcm_config& c = h->cfg;
-  if (K <= 0 || S <= 0) return fail(h, MCM_EINVAL, "K and S must be positive");
-  if (S > c.max_positions)  // HF modeling_clip.py:241-245 raises ValueError
-    return fail(h, MCM_ERANGE, "sequence length exceeds max_position_embeddings");
-  for (int64_t i = 0; i < (int64_t)K * S; ++i)
-    if (ids_host[i] < 0 || ids_host[i] >= c.vocab_size) return fail(h, MCM_EINVAL, "token id out of range");
-  hipStream_t s = (hipStream_t)stream;
+  int rc;
   const int D = c.t_width;
   const int chunk = c.max_prompt_tokens / S;  // prompts per pass
   for (int k0 = 0; k0 < K; k0 += chunk) {
@@ -1290,9 +1288,10 @@ int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_
     HIP_TRY(h, hipStreamSynchronize(s));  // pinned staging buffers are reused
     for (int k = 0; k < kc; ++k) {
       const int32_t* row = ids_host + (size_t)(k0 + k) * S;
-      int best = 0;  // first EOS = argmax id (HF modeling_clip.py:561-581)
+      const int32_t* slot = slot_host ? slot_host + (size_t)(k0 + k) * S : nullptr;
+      int best = 0;  // first EOS = argmax id (HF modeling_clip.py:561-581; CoOp: tokenized_prompts.argmax(-1))
       for (int j = 0; j < S; ++j) {
-        h->ids_pin[(size_t)k * S + j] = row[j];
+        h->ids_pin[(size_t)k * S + j] = (slot && slot[j] >= 0) ? -(slot[j] + 1) : row[j];
         if (row[j] > row[best]) best = j;
       }
       h->rowidx_pin[k] = k * S + best;
@@ -1303,9 +1302,14 @@ int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_
                               hipMemcpyHostToDevice, s));
     {
       Scope sc(h, s, MCM_KC_EMBED, 0.0);
-      HIP_TRY(h, launch_text_embed(h->ids_dev, W(h, "text_model.embeddings.token_embedding.weight"),
-                                   W(h, "text_model.embeddings.position_embedding.weight"), h->x,
-                                   kc, S, D, s));
+      if (slot_host)
+        HIP_TRY(h, launch_text_embed_ctx(h->ids_dev, W(h, "text_model.embeddings.token_embedding.weight"),
+                                         W(h, "text_model.embeddings.position_embedding.weight"), ctx_dev, h->x,
+                                         kc, S, D, n_ctx, n_sets, k0, s));
+      else
+        HIP_TRY(h, launch_text_embed(h->ids_dev, W(h, "text_model.embeddings.token_embedding.weight"),
+                                     W(h, "text_model.embeddings.position_embedding.weight"), h->x,
+                                     kc, S, D, s));
     }
     if ((rc = run_layers(h, s, h->txt, kc, S, true, false))) return rc;
     {
@@ -1318,6 +1322,39 @@ int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_
     }
   }
   return MCM_OK;
+}
+}  // namespace
+
+int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S, int32_t normalize,
+                       float* out_dev, void* stream) {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!ids_host || !out_dev) return fail(h, MCM_EINVAL, "null pointer");
+  const mcm_config& c = h->cfg;
+  if (K <= 0 || S <= 0) return fail(h, MCM_EINVAL, "K and S must be positive");
+  if (S > c.max_positions)  // HF modeling_clip.py:241-245 raises ValueError
+    return fail(h, MCM_ERANGE, "sequence length exceeds max_position_embeddings");
+  for (int64_t i = 0; i < (int64_t)K * S; ++i)
+    if (ids_host[i] < 0 || ids_host[i] >= c.vocab_size) return fail(h, MCM_EINVAL, "token id out of range");
+  return encode_text_passes(h, ids_host, nullptr, K, S, nullptr, 0, 0, normalize, out_dev, (hipStream_t)stream);
+}
+
+int mcm_encode_text_ctx(mcm_handle* h, const int32_t* ids_host, const int32_t* slot_host, int32_t K, int32_t S,
+                        const float* ctx_dev, int32_t n_ctx, int32_t n_sets, int32_t normalize, float* out_dev, void* stream) {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!ids_host || !slot_host || !ctx_dev || !out_dev) return fail(h, MCM_EINVAL, "null pointer");
+  const mcm_config& c = h->cfg;
+  if (K <= 0 || S <= 0 || n_ctx <= 0) return fail(h, MCM_EINVAL, "K, S and n_ctx must be positive");
+  if (n_sets != 1 && n_sets != K) return fail(h, MCM_EINVAL, "n_sets must be 1 (one context for every prompt) or K (one per prompt)");
+  if ((uintptr_t)ctx_dev & 15) return fail(h, MCM_EINVAL, "ctx_dev must be 16-byte aligned");
+  if (S > c.max_positions)  // as mcm_encode_text_ex
+    return fail(h, MCM_ERANGE, "sequence length exceeds max_position_embeddings");
+  for (int64_t i = 0; i < (int64_t)K * S; ++i) {
+    if (ids_host[i] < 0 || ids_host[i] >= c.vocab_size) return fail(h, MCM_EINVAL, "token id out of range");
+    if (slot_host[i] < -1 || slot_host[i] >= n_ctx) return fail(h, MCM_EINVAL, "context slot out of range (-1 .. n_ctx - 1)");
+  }
+  return encode_text_passes(h, ids_host, slot_host, K, S, ctx_dev, n_ctx, n_sets, normalize, out_dev, (hipStream_t)stream);
 }
 
 int mcm_score_features(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev,
@@ -1657,6 +1694,39 @@ int mcm_debug_op_text_embed(mcm_handle* h, const int32_t* ids_host, int32_t voca
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(ids_dev);
   if (refused) return fail(h, MCM_EINVAL, "launch_text_embed refused the shape (D % 4 == 0)");
+  HIP_TRY(h, e);
+  return MCM_OK;
+}
+
+// launch_text_embed_ctx: mcm_debug_op_text_embed with a slot per position — slot -1: tok[ids], slot j >= 0: row j of the prompt's
+// set in ctx [n_sets, n_ctx, D] (n_sets 1 or K).  Ids and slots come from the host and are checked here, as mcm_encode_text_ctx
+// checks its own, and folded into one word per position the same way; the call synchronises the stream.
+int mcm_debug_op_text_embed_ctx(mcm_handle* h, const int32_t* ids_host, const int32_t* slot_host, int32_t vocab,
+                                const float* tok_dev, const float* pos_dev, const float* ctx_dev, int32_t n_ctx, int32_t n_sets,
+                                float* x_dev, int32_t K, int32_t S, int32_t D, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (!ids_host || !slot_host || !tok_dev || !pos_dev || !ctx_dev || !x_dev || K <= 0 || S <= 0 || D <= 0 || vocab <= 0 || n_ctx <= 0)
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (n_sets != 1 && n_sets != K) return fail(h, MCM_EINVAL, "n_sets must be 1 or K");
+  const size_t nid = (size_t)K * S;
+  std::vector<int32_t> words(nid);
+  for (size_t i = 0; i < nid; ++i) {
+    if (ids_host[i] < 0 || ids_host[i] >= vocab) return fail(h, MCM_EINVAL, "token id out of range");
+    if (slot_host[i] < -1 || slot_host[i] >= n_ctx) return fail(h, MCM_EINVAL, "context slot out of range (-1 .. n_ctx - 1)");
+    words[i] = slot_host[i] >= 0 ? -(slot_host[i] + 1) : ids_host[i];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* words_dev = nullptr;
+  HIP_TRY(h, hipMalloc((void**)&words_dev, nid * sizeof(int32_t)));
+  hipError_t e = hipMemcpy(words_dev, words.data(), nid * sizeof(int32_t), hipMemcpyHostToDevice);
+  bool refused = false;
+  if (e == hipSuccess) {
+    e = launch_text_embed_ctx(words_dev, tok_dev, pos_dev, ctx_dev, x_dev, K, S, D, n_ctx, n_sets, 0, s);
+    refused = e == hipErrorInvalidValue;  // the launcher's own shape guard: nothing was launched
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(words_dev);
+  if (refused) return fail(h, MCM_EINVAL, "launch_text_embed_ctx refused the call (D % 4 == 0, ctx 16-byte aligned)");
   HIP_TRY(h, e);
   return MCM_OK;
 }

@@ -82,10 +82,17 @@ def prompt_bank(args, net, test_labels):
     """The [K,P] unit-norm bank for (labels, templates, tokenizer source), encoded once per `net`: a CLI run
     scores one ID and four OOD sets against the same bank (the reference re-encodes it every BATCH, :228-231;
     round 2 re-encoded it every dataset — 5 s per call with 80 templates x 1000 classes).  The key holds
-    everything the bank depends on; T and the score kind do not enter it."""
+    everything the bank depends on; T and the score kind do not enter it.  With `args.ctx` (a learned-context file, --ctx) the
+    prompts are CoOp's, the context vectors in place of the template's words (mcm_amd/prompts.py), and the key also holds the
+    file and `args.ctx_position`; without that attribute key and behaviour are what they always were."""
     templates = getattr(args, "templates", None)
+    ctx = getattr(args, "ctx", None)
     key = (tuple(str(c) for c in test_labels), tuple(templates) if templates else None,
            getattr(args, "tokenizer_dir", None) or getattr(args, "ckpt", ""))
+    if ctx:
+        if templates:
+            raise ValueError("a learned context (args.ctx) and a template ensemble (args.templates) exclude each other")
+        key += (str(ctx), getattr(args, "ctx_position", None) or "end")
     cache = getattr(net, "_bank_cache", None)
     if cache is None:
         try:
@@ -94,8 +101,13 @@ def prompt_bank(args, net, test_labels):
             cache = {}
     if key not in cache:
         cache.clear()  # one bank at a time (a bank is K x P floats; keep the handle small)
-        cache[key] = (encode_prompt_ensemble(args, net, test_labels, templates) if templates
-                      else encode_prompt_bank(args, net, test_labels))
+        if ctx:
+            from .prompts import encode_context_bank
+
+            cache[key] = encode_context_bank(args, net, test_labels)
+        else:
+            cache[key] = (encode_prompt_ensemble(args, net, test_labels, templates) if templates
+                          else encode_prompt_bank(args, net, test_labels))
     return cache[key]
 
 

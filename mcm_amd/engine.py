@@ -122,6 +122,7 @@ def load_library(harness: bool = False):
         L.mcm_debug_vision_front.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
         L.mcm_debug_op_pool_project.argtypes = [vp, vp, ctypes.c_int64, vp, i32, i32, i32, vp, vp, f32, vp, i32, vp, i32, vp]
         L.mcm_debug_op_text_embed.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]
+        L.mcm_debug_op_text_embed_ctx.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, i32, vp]
     L.mcm_encode_image_u8.argtypes = [vp, vp, i32, vp, vp]
     L.mcm_score_u8.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
     L.mcm_reduce_bank.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -142,6 +143,7 @@ def load_library(harness: bool = False):
     L.mcm_encode_image_raw.argtypes = [vp, vp, i32, vp, vp]
     L.mcm_encode_image_ex.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.mcm_encode_text_ex.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.mcm_encode_text_ctx.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp]
     L.mcm_score_histogram.argtypes = [vp, vp, ctypes.c_int64, vp, i32, vp, vp]
     L.mcm_maha_prepare.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.mcm_maha_score_features.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
@@ -187,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "mcm_neglabel_workspace_bytes", "mcm_neglabel_score_features",
     "mcm_local_workspace_bytes", "mcm_local_score_features", "mcm_encode_image_local", "mcm_score_glmcm",
     "mcm_vim_workspace_bytes", "mcm_vim_score_features",
+    "mcm_encode_text_ctx",
 ]
 HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
                         "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
@@ -196,7 +199,8 @@ HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant",
                         "mcm_debug_clear_faults", "mcm_debug_ln_cluster", "mcm_debug_ln_cluster_spin",
                         "mcm_debug_ln_cluster_deferred", "mcm_debug_ln_row", "mcm_debug_op_attention_split",
                         "mcm_debug_vision_front", "mcm_debug_op_pool_project", "mcm_debug_op_text_embed",
-                        "mcm_debug_op_act", "mcm_debug_op_attention_hd", "mcm_debug_op_attention_split_hd"]
+                        "mcm_debug_op_act", "mcm_debug_op_attention_hd", "mcm_debug_op_attention_split_hd",
+                        "mcm_debug_op_text_embed_ctx"]
 
 
 def _stream_ptr():
@@ -604,6 +608,37 @@ class NativeCLIP:
         out = torch.empty((K, self.geo.proj_dim), device=self.device, dtype=torch.float32)
         self._check(self._lib.mcm_encode_text_ex(self._h, ids.ctypes.data_as(ctypes.c_void_p), K, S,
                                                  int(bool(normalize)), out.data_ptr(), _stream_ptr()))
+        return out
+
+    def get_text_features_ctx(self, input_ids, slots, ctx, normalize: bool = False):
+        """`get_text_features` with learned context vectors in place of some token embeddings (CoOp's `PromptLearner.forward` +
+        `TextEncoder.forward`; include/mcm.h mcm_encode_text_ctx).  input_ids, slots: [K,S]; slots[k,s] = -1 for an ordinary
+        token, j in [0, n_ctx) for row j of the prompt's context, the id under it being a placeholder that only pooling reads.
+        ctx: tensor or array of any float dtype, [n_ctx, t_width] (one context for every prompt) or [K, n_ctx, t_width] (one
+        per prompt); it is widened exactly to fp32.  Returns [K,P] fp32, unit-norm rows with `normalize=True`."""
+        import torch
+
+        ids = np.ascontiguousarray(input_ids.detach().cpu().numpy() if hasattr(input_ids, "detach")
+                                   else np.asarray(input_ids), dtype=np.int32)
+        slot = np.ascontiguousarray(slots.detach().cpu().numpy() if hasattr(slots, "detach")
+                                    else np.asarray(slots), dtype=np.int32)
+        if ids.ndim != 2 or slot.shape != ids.shape:
+            raise ValueError("input_ids and slots must both be [K,S]")
+        K, S = ids.shape
+        if S > self.geo.max_positions:  # HF modeling_clip.py:241-245
+            raise ValueError(f"Sequence length must be less than max_position_embeddings (got {S})")
+        c = ctx if hasattr(ctx, "detach") else torch.from_numpy(np.ascontiguousarray(ctx))
+        if not c.is_floating_point():
+            raise ValueError(f"ctx must be a float tensor or array, got {c.dtype}")
+        if c.dim() not in (2, 3) or c.shape[-1] != self.geo.t_width or c.shape[-2] < 1:
+            raise ValueError(f"ctx must be [n_ctx,{self.geo.t_width}] or [K,n_ctx,{self.geo.t_width}], got {tuple(c.shape)}")
+        if c.dim() == 3 and c.shape[0] != K:
+            raise ValueError(f"a per-prompt ctx needs one context per prompt: first dimension {c.shape[0]}, K = {K}")
+        c = c.detach().to(device=self.device, dtype=torch.float32).contiguous()  # (every 16-bit float is an fp32 number)
+        out = torch.empty((K, self.geo.proj_dim), device=self.device, dtype=torch.float32)
+        self._check(self._lib.mcm_encode_text_ctx(self._h, ids.ctypes.data_as(ctypes.c_void_p),
+                                                  slot.ctypes.data_as(ctypes.c_void_p), K, S, c.data_ptr(), int(c.shape[-2]),
+                                                  K if c.dim() == 3 else 1, int(bool(normalize)), out.data_ptr(), _stream_ptr()))
         return out
 
     # -- fused hot-loop body -----------------------------------------------------------------
