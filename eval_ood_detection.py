@@ -1,9 +1,7 @@
-"""eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag
-and default is kept; additive flags only (`--weights`, `--dtype`, `--templates`, `--tokenizer-dir`,
-`--data-dir`, `--host-metrics`, `--synthetic-n`, `--synthetic`, `--predict`, `--maha-fit`, `--knn-k`, `--neg-*`, `--ctx*`).
-
-Drives the MI355X-native hot path: model → loaders → `get_ood_scores_clip` (ID once, then per OOD
-set) → AUROC / AUPR / FPR95 → log + CSV.
+"""eval_ood_detection.py — same CLI as the reference (eval_ood_detection.py:15-51): every flag and default is kept, the rest is
+additive.  Drives the MI355X-native hot path: model → loaders → the --score's record of mcm_amd/scores.py (`prepare` once, `score`
+for the ID set and then per OOD set; what a score accepts on the command line is that record's to say) → AUROC / AUPR / FPR95 →
+log + CSV.
 
 Data.  `--root-dir` is honoured the way the reference's loaders read it (utils/train_eval_util.py:87-146):
 `<root>/<in_dataset>/val/<class>/*` (ImageNet: `<root>/ImageNet/val`) for the ID set and
@@ -22,9 +20,9 @@ import os
 
 import numpy as np
 
+from mcm_amd.scores import METHODS, NO_REFINE, Run
 from utils.common import get_num_cls, get_test_labels, setup_seed
-from utils.detection_util import (get_and_print_results, get_Mahalanobis_score, get_mean_prec,
-                                  get_ood_scores_clip, print_measures)
+from utils.detection_util import get_and_print_results, print_measures
 
 # dataset sizes (external knowledge, as in the reference's loaders)
 N_ID = {"ImageNet": 50000, "ImageNet10": 500, "ImageNet20": 1000, "ImageNet100": 5000,
@@ -33,7 +31,7 @@ N_OOD = {"iNaturalist": 10000, "SUN": 10000, "places365": 10000, "dtd": 5640,
          "ImageNet10": 500, "ImageNet20": 1000}
 
 
-def process_args(argv=None):
+def parser():
     p = argparse.ArgumentParser(description="Evaluates MCM Score for CLIP",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--in_dataset", default="ImageNet", type=str,
@@ -54,7 +52,7 @@ def process_args(argv=None):
                             "ViT-H/14-laion2b"],
                    help="which pretrained img encoder to use")
     p.add_argument("--score", default="MCM", type=str,
-                   choices=["MCM", "energy", "max-logit", "entropy", "var", "maha", "knn", "neglabel", "GL-MCM", "vim"], help="score options")
+                   choices=list(METHODS), help="score options")
     # Mahalanobis baseline (--score maha), reference eval_ood_detection.py:38-44
     p.add_argument("--feat_dim", type=int, default=512)
     p.add_argument("--normalize", type=bool, default=False)
@@ -154,61 +152,39 @@ def process_args(argv=None):
     p.add_argument("--ctx-T", default=0.01, type=float,
                    help="--ctx: the temperature of the MCM-family and GL-MCM scores (--T is ignored there: the contexts were "
                         "trained through softmax(100 cos), and --T is an int by the reference's contract)")
+    return p
+
+
+def process_args(argv=None):
+    p = parser()
     args = p.parse_args(argv)
+    method = METHODS[args.score]   # what this score accepts is the record's to say (mcm_amd/scores.py)
+    asked = {"ctx": bool(args.ctx), "fp16x2": args.dtype == "fp16x2", "refine": args.refine_threshold in ("on", "exact"),
+             "maha_fit": args.maha_fit == "device", "predict": bool(args.predict)}
+
+    def refused(*switches):
+        for switch in switches:
+            if asked[switch] and switch in method.refuse:
+                p.error(method.refuse[switch])
+
     if args.ctx:
         if args.templates:
             p.error("--ctx and --templates exclude each other (a learned context replaces the template's words)")
-        if args.score in ("maha", "knn"):
+        if method.bank == "none":
             p.error(f"--ctx needs a score with a prompt bank: --score {args.score} has none")
-        if args.score == "neglabel":
-            p.error("--ctx is not available with --score neglabel (its mined negatives are template prompts and would sit in another "
-                    "space than the ID rows)")
+        refused("ctx")
         if not (args.ctx_T > 0.0 and np.isfinite(args.ctx_T)):
             p.error("--ctx-T must be positive and finite")
-        if args.score != "vim":  # (vim's logits keep --vim-T)
+        if method.ctx_T:
             args.T = args.ctx_T
-    if args.score == "GL-MCM":
-        if not np.isfinite(args.gl_lambda):
-            p.error("--gl-lambda must be finite")
-        if args.dtype == "fp16x2":
-            p.error("--score GL-MCM has no split-activation arm: --dtype fp16x2 is not available with it")
-        if args.refine_threshold in ("on", "exact"):
-            p.error("--refine-threshold on / exact is not available with --score GL-MCM (no re-scoring arm for the local term)")
-        if args.predict:
-            p.error("--predict is not available with --score GL-MCM")
-        args.refine_threshold = "off"  # auto resolves to off
-    if args.score == "neglabel":
-        if not args.neg_words:
-            p.error("--score neglabel needs --neg-words FILE (one candidate word per line)")
-        if args.neg_count < 0 or not 0.0 < args.neg_frac <= 1.0 or not 0.0 <= args.neg_quantile <= 1.0:
-            p.error("--neg-count must be >= 0, --neg-frac in (0, 1], --neg-quantile in [0, 1]")
-        if not 1 <= args.neg_groups <= 1024:
-            p.error("--neg-groups G: G must be 1..1024")
-        if not (args.neg_T > 0.0 and np.isfinite(args.neg_T)):
-            p.error("--neg-T must be positive and finite")
-    if args.score == "vim":
-        if args.vim_dim < 0:
-            p.error("--vim-dim D: D must be 0 or 1..proj_dim - 1")
-        if not (args.vim_T > 0.0 and np.isfinite(args.vim_T)):
-            p.error("--vim-T must be positive and finite")
-    if not 0 <= args.knn_k <= 1024:
+    method.check_args(args, p.error)
+    if not 0 <= args.knn_k <= 1024:   # (for every score: the flag is accepted with all of them)
         p.error("--knn-k K: K must be 1..1024 (0 = chosen from the bank size)")
-    if args.score in ("knn", "neglabel", "vim") and args.refine_threshold in ("on", "exact"):
-        p.error("--refine-threshold on needs a 16-bit --dtype and an MCM-family --score")
-    if args.score == "vim":
-        args.refine_threshold = "off"  # auto resolves to off
-    if args.maha_fit == "device" and args.score != "maha":
-        p.error("--maha-fit device needs --score maha (no other score fits anything)")
-    if args.predict:
-        if args.score in ("maha", "knn"):
-            p.error("--predict needs a concept-matching --score (MCM, energy, max-logit, entropy, var): the training-set "
-                    "baselines (--score maha, --score knn) have no prompt bank to match against")
-        if args.score == "neglabel":
-            p.error("--predict is not available with --score neglabel (its kernel returns group masses, not matched concepts)")
-        if args.score == "vim":
-            p.error("--predict is not available with --score vim (its kernel returns a residual and an energy, not matched concepts)")
-        if not 1 <= args.predict <= 8:
-            p.error("--predict K: K must be 1..8")
+    refused("fp16x2", "refine", "maha_fit", "predict")
+    if args.refine_threshold == "auto":
+        args.refine_threshold = method.auto_refine
+    if args.predict and not 1 <= args.predict <= 8:
+        p.error("--predict K: K must be 1..8")
     if args.decoder:
         os.environ["MCM_GPU_JPEG"] = "1" if args.decoder == "device" else "0"
     if args.templates:
@@ -283,27 +259,6 @@ def _note_pillow_files(net, sources, what, log):
     net.__dict__["_pillow_files_seen"] = total
 
 
-def _score_set(args, net, loader, test_labels, what, log, rank, on_dev, in_dist=False):
-    """Scores of one set — `get_ood_scores_clip`, or with --predict `get_ood_predictions_clip`: the same scores, plus the
-    set's predictions written to predictions_<what>.npz (rank 0) and, for the ID set, the zero-shot accuracy line."""
-    if not args.predict:
-        return get_ood_scores_clip(args, net, loader, test_labels, in_dist=in_dist, device_out=on_dev)
-    from mcm_amd.detection import get_ood_predictions_clip, zero_shot_accuracy
-
-    scores, idx, prob, labels = get_ood_predictions_clip(args, net, loader, test_labels, topk=args.predict, device_out=True)
-    if rank == 0:
-        idx_h, labels_h = idx.cpu().numpy(), labels.cpu().numpy()
-        np.savez(os.path.join(args.log_directory, f"predictions_{what}.npz"), idx=idx_h, prob=prob.cpu().numpy(),
-                 scores=scores.cpu().numpy(), labels=labels_h)
-        if in_dist:
-            k5 = min(5, args.predict)
-            acc = zero_shot_accuracy(idx_h, labels_h, ks=(1, k5))
-            log.debug(f"zero-shot ID accuracy: top-1 {100 * acc[1]:.2f} %, top-{k5} {100 * acc[k5]:.2f} % over {len(labels_h)} images "
-                      "(loader label i is taken to be concept i, as in the reference's loaders)"
-                      + ("" if args.weights else " — seeded synthetic weights: a plumbing check, not an accuracy"))
-    return scores if on_dev else scores.cpu().numpy().astype(np.float32, copy=False)
-
-
 def main(argv=None):
     import json
 
@@ -311,10 +266,10 @@ def main(argv=None):
 
     from mcm_amd import dist as mdist
     from mcm_amd.config import HUB_IDS
-    from mcm_amd.detection import maha_file_name
     from mcm_amd.engine import build_model
 
     args = process_args(argv)
+    method = METHODS[args.score]
     setup_seed(args.seed)
     assert torch.cuda.is_available()
     ndev = torch.cuda.device_count()
@@ -342,12 +297,7 @@ def main(argv=None):
     # the split-activation workspace of an fp16 handle (include/mcm.h mcm_config.x2_max_batch): the whole run goes
     # through that arm with --dtype fp16x2 (full batch: twice the activation bytes); threshold refinement re-scores a few hundred
     # images, for which half the batch costs nothing extra; otherwise the workspace is not allocated at all
-    # the training-set baselines (no prompt bank) and neglabel (a bank of its own): scores come back as host arrays, and
-    # there is no threshold refinement
-    # (GL-MCM uses the prompt bank, and vim the prompt bank with a basis behind it, but like them they have no re-scoring
-    # arm and hand back host arrays)
-    no_bank = args.score in ("maha", "knn", "neglabel", "GL-MCM", "vim")
-    will_refine = args.refine_threshold != "off" and not no_bank
+    will_refine = args.refine_threshold != "off" and method.refine
     x2_batch = 0 if args.dtype == "fp16x2" else (max(1, args.batch_size // 2) if (args.dtype == "fp16" and will_refine) else -1)
     net = build_model(args.CLIP_ckpt, weights=args.weights, device=dev, precision=args.dtype,
                       max_batch=args.batch_size, synthetic_regime=args.synthetic_weights,
@@ -373,7 +323,7 @@ def main(argv=None):
             raise SystemExit(f"--ctx {args.ctx}: context vectors are {c.ctx.shape[-1]} wide, the text tower of {args.CLIP_ckpt} {net.geo.t_width}")
         log.debug(f"--ctx {args.ctx}: n_ctx = {c.n_ctx}, {'per-class (' + str(c.ctx.shape[0]) + ' classes)' if c.per_class else 'shared'} "
                   f"context, class name at the {args.ctx_position}"
-                  + (f"; --T is ignored, the temperature is --ctx-T {args.ctx_T}" if args.score != "vim" else ""))
+                  + (f"; --T is ignored, the temperature is --ctx-T {args.ctx_T}" if method.ctx_T else ""))
     args.ckpt = HUB_IDS[args.CLIP_ckpt]  # reference utils/train_eval_util.py:19-22 (ckpt_mapping)
     if args.in_dataset == "ImageNet10":
         out_datasets = ["ImageNet20"]
@@ -384,101 +334,26 @@ def main(argv=None):
     sources = {}
     test_loader = _loader(args, net, "id", N_ID[args.in_dataset], False, sources)
     test_labels = get_test_labels(args, test_loader)
-    on_dev = not args.host_metrics and not no_bank  # scores stay in HBM; three metrics come back
-    if args.score == "maha":  # reference eval_ood_detection.py:72-79
-        args.feat_dim = net.geo.proj_dim
-        os.makedirs(args.template_dir, exist_ok=True)
-        # world_size > 1: the host fit (a host-side float64 step over the training features) runs on rank 0 only; with
-        # --maha-fit device every rank fits its shard of the training set and the running sums are all-reduced (rank 0 writes
-        # the files).  Either way the two statistics are then broadcast (RCCL) and every rank scores its own shard of each
-        # test set (get_Mahalanobis_score)
-        if args.generate and (rank == 0 or args.maha_fit == "device"):
-            n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
-            train_loader = _loader(args, net, "train", n_train, False, sources)
-            if args.maha_fit == "device":
-                from mcm_amd.detection import get_mean_prec_device
+    on_dev = not args.host_metrics and method.on_dev  # scores stay in HBM; three metrics come back
 
-                get_mean_prec_device(args, net, train_loader)
-            else:
-                get_mean_prec(args, net, train_loader)
-        # like the reference (:77-78) the statistics are always read back from the files get_mean_prec wrote —
-        # or that an earlier run wrote, which is what `--generate ""` (argparse's only falsy bool) is for
-        stats = {"classwise_mean": torch.empty((args.n_cls, args.feat_dim)), "precision": torch.empty((args.feat_dim, args.feat_dim))}
-        missing = None
-        if rank == 0:
-            for what in ("classwise_mean", "precision"):
-                f = os.path.join(args.template_dir, maha_file_name(args, what))
-                if not os.path.exists(f):
-                    missing = f
-                    break
-                stats[what] = torch.load(f, map_location="cpu").float().contiguous()
-        if ws > 1:  # every rank learns whether rank 0 found the files BEFORE anybody waits in the broadcast
-            ok = torch.tensor([0.0 if missing else 1.0])
-            mdist.broadcast_tensors([ok], src=0)
-            if float(ok[0]) == 0.0 and missing is None:
-                missing = "the statistics files (see rank 0's message)"
-        if missing:
-            raise SystemExit(f"--generate is off and {missing} does not exist: run once with --generate True")
-        if ws > 1:
-            mdist.broadcast_tensors([stats["classwise_mean"], stats["precision"]], src=0)
-        classwise_mean, precision = stats["classwise_mean"], stats["precision"]
-        in_score = get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_dist=True)
-    elif args.score == "knn":
-        from mcm_amd.detection import get_knn_bank, get_knn_score, knn_auto_k
-
-        # every rank encodes its shard of the training set; the bank is all-gathered and stays in HBM for the run
+    def train_loader():
         n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
-        knn_bank = get_knn_bank(args, net, _loader(args, net, "train", n_train, False, sources))
-        knn_k = args.knn_k or knn_auto_k(len(knn_bank))
-        if knn_k > len(knn_bank):
-            raise SystemExit(f"--knn-k {knn_k} exceeds the bank's {len(knn_bank)} rows")
-        log.debug(f"--score knn: k = {knn_k}{'' if args.knn_k else ' (auto)'}, bank of {len(knn_bank)} unit-norm training features "
-                  f"x {knn_bank.shape[1]} ({sources['train']['kind']})")
-        in_score = get_knn_score(args, net, test_loader, knn_bank, knn_k)
-    elif args.score == "neglabel":
-        from mcm_amd.detection import get_neglabel_bank, get_neglabel_score
+        return _loader(args, net, "train", n_train, False, sources)
 
-        with open(args.neg_words, encoding="utf-8") as f:
-            neg_words = f.read().splitlines()
-        log.debug(f"--score neglabel: --T {args.T} is ignored; the softmax temperature is --neg-T {args.neg_T}")
-        neg_bank = get_neglabel_bank(args, net, test_labels, neg_words)
-        log.debug(f"--score neglabel: K = {neg_bank['K']} ID labels, C = {neg_bank['C']} candidate words from {args.neg_words}, "
-                  f"M = {neg_bank['M']} kept, G = {neg_bank['G']} groups of gs = {neg_bank['gs']}; kept d from "
-                  f"{float(neg_bank['d'].min()):.6f} to {float(neg_bank['d'].max()):.6f} (quantile {args.neg_quantile})")
-        in_score = get_neglabel_score(args, net, test_loader, neg_bank)
-    elif args.score == "vim":
-        from mcm_amd.detection import get_vim_fit, get_vim_score, vim_principal_dim
+    run = Run(args, net, log, rank, ws, sources, test_labels, train_loader, on_dev)
 
-        try:  # the geometry is known here
-            vim_principal_dim(net.geo.proj_dim, args.vim_dim)
-        except ValueError as e:
-            raise SystemExit(str(e))
-        log.debug(f"--score vim: --T {args.T} is ignored; the temperature of the logits is --vim-T {args.vim_T}")
-        n_train = min(N_ID[args.in_dataset], args.max_count * args.n_cls) if args.subset else N_ID[args.in_dataset]
-        try:
-            vim_fit = get_vim_fit(args, net, _loader(args, net, "train", n_train, False, sources), test_labels)
-        except ValueError as e:  # the subspace is not determined, or alpha is not a number
-            raise SystemExit(str(e))
-        lam = vim_fit["eigenvalues"]
-        log.debug(f"--score vim: D = {vim_fit['D']}{'' if args.vim_dim else ' (auto)'}, R = {vim_fit['R']}, n = {vim_fit['n']} unit-norm "
-                  f"training features ({sources['train']['kind']}), alpha = {vim_fit['alpha']:.6g}, lambda_D = {lam[vim_fit['R']]:.6e}, "
-                  f"lambda_(D+1) = {lam[vim_fit['R'] - 1]:.6e}, lambda_max = {lam[-1]:.6e}")
-        if vim_fit["alpha"] <= 0.0:
-            log.debug("NOTE: alpha is not positive, so the residual enters the score with the wrong sign (seeded synthetic weights "
-                      "can produce this; a trained checkpoint should not)")
-        in_score = get_vim_score(args, net, test_loader, vim_fit)
-    elif args.score == "GL-MCM":
-        from mcm_amd.detection import get_glmcm_scores
+    def score_set(loader, what, in_dist):   # (the one place every set of every score goes through)
+        scores = method.score(run, state, loader, what, in_dist)
+        if method.note_pillow:
+            _note_pillow_files(net, sources, what, log)
+        return scores
 
-        log.debug(f"--score GL-MCM: -(S_G + {args.gl_lambda} S_L) at T = {args.T}, {net.local_rows} patch rows per image")
-        in_score = get_glmcm_scores(args, net, test_loader, test_labels)
-    else:
-        in_score = _score_set(args, net, test_loader, test_labels, "id", log, rank, on_dev, in_dist=True)
-        _note_pillow_files(net, sources, "id", log)
+    state = method.prepare(run)
+    in_score = score_set(test_loader, "id", True)
     net.warn_if_saturated(f"the ID set {args.in_dataset}")
     refiner, net32 = None, None
-    refinable = not no_bank and args.dtype in ("fp16", "bf16")  # (fp16x2 / fp32 runs ARE exact-grade arms; with
-                                                                       # --host-metrics the scores are host arrays: refined in place too)
+    refinable = method.refine and args.dtype in ("fp16", "bf16")  # (fp16x2 / fp32 runs ARE exact-grade arms; with
+                                                                  # --host-metrics the scores are host arrays: refined in place too)
     if args.refine_threshold != "off" and refinable:
         from mcm_amd.detection import prompt_bank
         from mcm_amd.refine import Rescorer, ThresholdRefiner
@@ -502,8 +377,8 @@ def main(argv=None):
         if second is not None:
             log.debug("threshold refinement, inner window +-%.2e: %d ID images re-scored by the exact-fp32 arm"
                       % (refiner.stats["delta2"], refiner.stats["rescored_exact"]["id"]))
-    elif args.refine_threshold in ("on", "exact"):
-        raise SystemExit("--refine-threshold on needs a 16-bit --dtype and an MCM-family --score")
+    elif args.refine_threshold in ("on", "exact"):   # (an MCM-family score at an exact-grade --dtype, or --score maha)
+        raise SystemExit(NO_REFINE)
     auroc_list, aupr_list, fpr_list = [], [], []
     result = {"in_score": in_score, "out_scores": {}, "rank": rank, "world_size": ws, "sources": sources,
               "log_directory": args.log_directory, "batch_size": args.batch_size}
@@ -511,24 +386,12 @@ def main(argv=None):
         log.debug(f"Evaluting OOD dataset {out_dataset}")
         ood_loader = _loader(args, net, out_dataset, N_OOD[out_dataset], True, sources)
         log.debug(f"data source: {sources[out_dataset]}")
-        if args.score == "maha":
-            out_score = get_Mahalanobis_score(args, net, ood_loader, classwise_mean, precision, in_dist=False)
-        elif args.score == "knn":
-            out_score = get_knn_score(args, net, ood_loader, knn_bank, knn_k)
-        elif args.score == "neglabel":
-            out_score = get_neglabel_score(args, net, ood_loader, neg_bank)
-        elif args.score == "vim":
-            out_score = get_vim_score(args, net, ood_loader, vim_fit)
-        elif args.score == "GL-MCM":
-            out_score = get_glmcm_scores(args, net, ood_loader, test_labels)
-        else:
-            out_score = _score_set(args, net, ood_loader, test_labels, out_dataset, log, rank, on_dev)
-            _note_pillow_files(net, sources, out_dataset, log)
-            if refiner is not None:
-                set_loaders[out_dataset] = ood_loader
-                refiner.apply(out_dataset, out_score if on_dev else torch.from_numpy(out_score))
-                log.debug(f"threshold refinement: {refiner.stats['rescored'][out_dataset]} images of {out_dataset} re-scored"
-                          + (f", {refiner.stats['rescored_exact'][out_dataset]} of them by the exact-fp32 arm" if second is not None else ""))
+        out_score = score_set(ood_loader, out_dataset, False)
+        if refiner is not None:
+            set_loaders[out_dataset] = ood_loader
+            refiner.apply(out_dataset, out_score if on_dev else torch.from_numpy(out_score))
+            log.debug(f"threshold refinement: {refiner.stats['rescored'][out_dataset]} images of {out_dataset} re-scored"
+                      + (f", {refiner.stats['rescored_exact'][out_dataset]} of them by the exact-fp32 arm" if second is not None else ""))
         result["out_scores"][out_dataset] = out_score
         net.warn_if_saturated(out_dataset)
         if rank == 0:

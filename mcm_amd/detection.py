@@ -164,36 +164,17 @@ def _scores_over_shards(loader, device, device_out, score_batch):
     [len(loader.dataset)] scores as a device tensor (`device_out`) or a float32 ndarray."""
     import torch
 
-    rank, ws = mdist.world()
     n_total = len(loader.dataset)
-    by_index = True  # this rank's shard is the contiguous index range shard_range gives
-    mine = lambda i: True  # noqa: E731
-    batches = loader
-    if ws > 1:
-        lo, hi = mdist.shard_range(n_total, rank, ws)
-        batches = shard_loader(loader, lo, hi)
-        if batches is None:  # an opaque iterable: batch-range shards (every rank still pays its decode)
-            by_index = False
-            nb = len(loader)
-            blo, bhi = mdist.shard_range(nb, rank, ws)
-            batches = loader
-            mine = lambda i: blo <= i < bhi  # noqa: E731
-    parts = []
-    for batch_idx, (images, _labels) in enumerate(batches):
-        if not mine(batch_idx):
-            continue
-        parts.append(score_batch(images))
-    local = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=device)
-    if mdist.group_active():  # (also a 1-rank group: the collective really runs — RCCL on a GPU box)
-        if by_index:
-            full = mdist.all_gather_scores(local, n_total)
-        else:  # batch-range shards of an opaque loader: sizes follow the batch split
-            full = _gather_batch_shards(local, n_total, ws)
-    else:
-        full = local
+    batches, by_index = _shard_batches(loader, n_total, None, opaque_ok=True)
+    parts = [score_batch(images) for images, _labels in batches]
+    if by_index:  # (also in a 1-rank group: the collective really runs — RCCL on a GPU box)
+        full = _gather_shards(parts, n_total, device)
+    else:  # batch-range shards of an opaque loader: sizes follow the batch split
+        local = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=device)
+        full = _gather_batch_shards(local, n_total, mdist.world()[1]).detach()[:n_total]
     if device_out:
-        return full.detach()[:n_total]
-    return full.detach().cpu().numpy().astype(np.float32, copy=False)[:n_total].copy()
+        return full
+    return full.cpu().numpy().astype(np.float32, copy=False).copy()
 
 
 def get_glmcm_scores(args, net, loader, test_labels, device_out=False):
@@ -233,31 +214,21 @@ def get_ood_predictions_clip(args, net, loader, test_labels, topk=5, device_out=
     if not hasattr(net, "score_images"):
         raise TypeError("net must be a mcm_amd NativeCLIP (fused score_images path); there is no eager fallback")
     topk = int(topk)
-    rank, ws = mdist.world()
     n_total = len(loader.dataset)
     with torch.no_grad():
         text_features = prompt_bank(args, net, test_labels)
         dev = text_features.device
-        batches = loader
-        if ws > 1:
-            lo, hi = mdist.shard_range(n_total, rank, ws)
-            batches = shard_loader(loader, lo, hi)
-            if batches is None:
-                raise TypeError("get_ood_predictions_clip under world_size > 1 needs a loader with .shard(lo, hi) or a "
-                                "torch DataLoader over a map-style dataset")
+        batches, _ = _shard_batches(loader, n_total, "get_ood_predictions_clip under world_size > 1 needs a loader with "
+                                    ".shard(lo, hi) or a torch DataLoader over a map-style dataset")
         parts = ([], [], [], [])
         for images, labels in batches:
             s, i, p = net.score_images(images, text_features, float(args.T), args.score, topk=topk)
             for dst, t in zip(parts, (s, i, p, torch.as_tensor(labels).reshape(-1).to(device=dev, dtype=torch.int64))):
                 dst.append(t)
-        empty = (torch.empty(0, dtype=torch.float32, device=dev), torch.empty((0, topk), dtype=torch.int32, device=dev),
-                 torch.empty((0, topk), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
-        full = [torch.cat(p) if p else e for p, e in zip(parts, empty)]
-        if mdist.group_active():
-            full = [mdist.all_gather_rows(t, n_total) for t in full]
-    full = [t.detach()[:n_total] for t in full]
+        full = tuple(_gather_shards(p, n_total, dev, width, dtype) for p, (width, dtype) in zip(parts, (
+            (None, torch.float32), (topk, torch.int32), (topk, torch.float32), (None, torch.int64))))
     if device_out:
-        return tuple(full)
+        return full
     return tuple(t.cpu().numpy().copy() for t in full)
 
 
@@ -302,18 +273,29 @@ def shard_loader(loader, lo: int, hi: int):
     return DataLoader(Subset(ds, range(lo, hi)), **kw)
 
 
-def _shard_batches(loader, n, what):
-    """This rank's (images, labels) batches of samples [0, n) of `loader.dataset`, in order: all of them for one rank, the
-    rank's `shard_range` under world_size > 1, where a loader `shard_loader` cannot split by index is refused (`what`: the
-    --score named in the refusal, raised by this call and not by the first batch).  The last batch is cut to the range's
-    end, images and labels alike."""
+def _my_range(n):
+    """This rank's contiguous share [lo, hi) of n items in order: all of them for one rank, else its `shard_range`."""
     rank, ws = mdist.world()
-    batches, lo, hi = loader, 0, n
-    if ws > 1:
-        lo, hi = mdist.shard_range(n, rank, ws)
-        batches = shard_loader(loader, lo, hi)
-        if batches is None:
-            raise TypeError(f"--score {what} under world_size > 1 needs a loader that can be sharded by index")
+    return mdist.shard_range(n, rank, ws) if ws > 1 else (0, n)
+
+
+_BY_INDEX = "--score {} under world_size > 1 needs a loader that can be sharded by index"
+
+
+def _shard_batches(loader, n, what, opaque_ok=False):
+    """(batches, by_index): this rank's (images, labels) batches of samples [0, n) of `loader.dataset`, in order — all of them
+    for one rank, the rank's `shard_range` under world_size > 1, the last batch cut to the range's end, images and labels alike
+    (by_index: `_gather_shards` joins the ranks' results).  A loader `shard_loader` cannot split by index is refused with the
+    TypeError text `what` (raised by this call and not by the first batch) — or, with `opaque_ok`, walked by every rank, which
+    keeps its `shard_range` of the BATCHES (every rank still pays its decode; by_index is False: only the owning rank knows its
+    shard's size, `_gather_batch_shards` joins them)."""
+    lo, hi = _my_range(n)
+    batches = shard_loader(loader, lo, hi) if mdist.world()[1] > 1 else loader
+    if batches is None:
+        if not opaque_ok:
+            raise TypeError(what)
+        blo, bhi = _my_range(len(loader))
+        return (batch for i, batch in enumerate(loader) if blo <= i < bhi), False
 
     def walk():
         seen = 0
@@ -325,7 +307,7 @@ def _shard_batches(loader, n, what):
             yield images, labels
             seen += images.shape[0]
 
-    return walk()
+    return walk(), True
 
 
 def _feature_home(args, net):
@@ -334,16 +316,29 @@ def _feature_home(args, net):
     return getattr(net, "device", None) or "cpu", int(P)
 
 
-def _gather_shards(parts, n_total, device, width=None):
-    """What `_shard_batches` produced on every rank, in dataset order, on every rank: this rank's `parts` joined (no part: an
-    empty fp32 tensor on `device`, [0] scores or [0, width] rows), all-gathered where a process group exists, cut to n_total."""
+def _gather_shards(parts, n_total, device, width=None, dtype=None):
+    """What `_shard_batches` produced by index on every rank, in dataset order, on every rank: this rank's `parts` joined (no
+    part: an empty tensor of `dtype`, fp32 by default, on `device`: [0] values or [0, width] rows), all-gathered where a process
+    group exists, cut to n_total."""
     import torch
 
-    shape = (0,) if width is None else (0, width)
-    local = torch.cat(parts) if parts else torch.empty(shape, dtype=torch.float32, device=device)
+    dtype = dtype or torch.float32
+    local = torch.cat(parts) if parts else torch.empty((0,) if width is None else (0, width), dtype=dtype, device=device)
     if mdist.group_active():
-        local = (mdist.all_gather_scores if width is None else mdist.all_gather_rows)(local, n_total)
+        scores = width is None and dtype == torch.float32
+        local = (mdist.all_gather_scores if scores else mdist.all_gather_rows)(local, n_total)
     return local.detach()[:n_total]
+
+
+def _score_loader(loader, n, what, device, fn):
+    """The body of the feature-space scores: samples [0, n) of `loader` scored by `fn(images) -> [b]` device scores, batch by
+    batch over this rank's shard (`what`: the --score named where the loader cannot be sharded by index), gathered to every
+    rank: a float32 ndarray [n]."""
+    import torch
+
+    with torch.no_grad():
+        out = [fn(images) for images, _labels in _shard_batches(loader, n, _BY_INDEX.format(what))[0]]
+    return _gather_shards(out, n, device).cpu().numpy().astype(np.float32)
 
 
 def get_mean_prec(args, net, train_loader):
@@ -417,47 +412,34 @@ def get_mean_prec_device(args, net, train_loader, return_cov=False):
     if not hasattr(net, "maha_fit_accumulate"):
         raise TypeError("get_mean_prec_device needs a net with maha_fit_state / maha_fit_accumulate (a NativeCLIP); "
                         "get_mean_prec is the host route")
-    rank, ws = mdist.world()
+    import itertools
+
+    rank = mdist.world()[0]
     n_total = len(train_loader.dataset)
     bs = int(getattr(train_loader, "batch_size", None) or args.batch_size)
     n_batches = -(-n_total // bs)
-    batches, lo, hi = train_loader, 0, n_total
-    if ws > 1:
-        lo, hi = mdist.shard_range(n_total, rank, ws)
-        batches = shard_loader(train_loader, lo, hi)
-        if batches is None:
-            raise TypeError("--score maha under world_size > 1 needs a loader that can be sharded by index")
+    batches = _shard_batches(train_loader, n_total, _BY_INDEX.format("maha"))[0]
+    g0 = _my_range(n_total)[0]
 
-    def features(images):
-        f = net.get_image_features(pixel_values=images).float()
+    def features(batch):
+        f = net.get_image_features(pixel_values=batch[0]).float()
         if args.normalize:
             f = f / f.norm(dim=-1, keepdim=True)
-        return f
+        return f, batch[1]
 
     n_cb = np.zeros((args.n_cls, n_batches), np.float64)
     with torch.no_grad():
-        it = iter(batches) if hi > lo else iter(())
-        first = None
+        first = []
         shift = torch.zeros(args.feat_dim, dtype=torch.float32)
-        if rank == 0 and hi > lo:  # the batch that starts at global sample 0
-            images, labels = next(it)
-            first = (features(images), labels)
-            shift = first[0].mean(dim=0)
+        if rank == 0:  # the batch that starts at global sample 0
+            first = [features(batch) for batch in itertools.islice(batches, 1)]
+            if first:
+                shift = first[0][0].mean(dim=0)
         mdist.broadcast_tensors([shift], src=0)
         state = net.maha_fit_state(shift)
         dev = state["gram"].device
         rows = torch.zeros((n_batches, state["gram"].shape[0]), dtype=torch.float32, device=dev)
-        seen = 0
-        while seen < hi - lo:
-            if first is not None:
-                (f, labels), first = first, None
-            else:
-                try:
-                    images, labels = next(it)
-                except StopIteration:
-                    break
-                f = features(images)
-            f, g0 = f[: hi - lo - seen], lo + seen
+        for f, labels in itertools.chain(first, map(features, batches)):
             b = f.shape[0]
             net.maha_fit_accumulate(f, state)
             if g0 < n_batches:  # the rows the reference's batch indices select
@@ -467,7 +449,7 @@ def get_mean_prec_device(args, net, train_loader, return_cov=False):
             lab = lab.astype(np.int64).reshape(-1)[:b]
             keep = lab < args.n_cls
             np.add.at(n_cb, (lab[keep], (g0 + np.arange(b)[keep]) // bs), 1.0)
-            seen += b
+            g0 += b
         gram, fsum = state["gram"], state["sum"]
         n_t = torch.tensor([float(state["n"])], dtype=torch.float64, device=dev)
         ncb_t = torch.from_numpy(n_cb).to(dev)
@@ -503,20 +485,19 @@ def get_Mahalanobis_score(args, net, test_loader, classwise_mean, precision, in_
     torch.mm pairs replaced by the native kernels (one quadratic form + C dot products per image).
     Keeps the reference's loop rule that for OOD sets (`in_dist=False`) iteration stops at batch
     `len(dataset) // batch_size`, i.e. a trailing partial batch is NOT scored (:185-186)."""
-    import torch
-
     state = net.maha_prepare(classwise_mean, precision)
     total_len = len(test_loader.dataset)
     # the samples the reference scores: everything for the ID set, whole batches only for an OOD set
     n_scored = total_len if in_dist else min(total_len, (total_len // args.batch_size) * args.batch_size)
-    out = []
-    with torch.no_grad():  # image-sharded like get_ood_scores_clip: a contiguous index range per rank, all-gathered at the end
-        for images, _labels in _shard_batches(test_loader, n_scored, "maha"):
-            features = net.get_image_features(pixel_values=images).float()
-            if args.normalize:
-                features = features / features.norm(dim=-1, keepdim=True)
-            out.append(net.maha_scores(features, state))
-    return _gather_shards(out, n_scored, state["prec"].device).cpu().numpy().astype(np.float32)
+
+    def score(images):
+        features = net.get_image_features(pixel_values=images).float()
+        if args.normalize:
+            features = features / features.norm(dim=-1, keepdim=True)
+        return net.maha_scores(features, state)
+
+    # image-sharded like get_ood_scores_clip: a contiguous index range per rank, all-gathered at the end
+    return _score_loader(test_loader, n_scored, "maha", state["prec"].device, score)
 
 
 def knn_auto_k(n_bank):
@@ -543,7 +524,8 @@ def get_knn_bank(args, net, train_loader):
         raise TypeError("get_knn_bank needs a net with knn_scores (a NativeCLIP); there is no eager fallback")
     n_total = len(train_loader.dataset)
     with torch.no_grad():
-        parts = [_unit_image_features(net, images) for images, _labels in _shard_batches(train_loader, n_total, "knn")]
+        batches = _shard_batches(train_loader, n_total, _BY_INDEX.format("knn"))[0]
+        parts = [_unit_image_features(net, images) for images, _labels in batches]
         return _gather_shards(parts, n_total, *_feature_home(args, net)).contiguous()
 
 
@@ -552,16 +534,11 @@ def get_knn_score(args, net, loader, bank, k):
     of `bank` (`get_knn_bank`) — the distance to the k-th nearest training feature; larger = more OOD.  Sharded and gathered
     like `get_ood_scores_clip`; EVERY sample is scored (the drop-the-last-batch rule belongs to the reference's Mahalanobis
     function only).  Returns a float32 ndarray [len(loader.dataset)]."""
-    import torch
-
     k = int(k)
     if not 1 <= k <= len(bank):
         raise ValueError(f"--score knn: k = {k} needs 1 <= k <= the bank's {len(bank)} rows")
-    n_total = len(loader.dataset)
-    with torch.no_grad():
-        out = [net.knn_scores(_unit_image_features(net, images), bank, k)
-               for images, _labels in _shard_batches(loader, n_total, "knn")]
-    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
+    return _score_loader(loader, len(loader.dataset), "knn", bank.device,
+                         lambda images: net.knn_scores(_unit_image_features(net, images), bank, k))
 
 
 NEG_MAX_GROUPS = 1024  # MCM_NEG_MAX_GROUPS of include/mcm.h
@@ -586,9 +563,8 @@ def _candidate_features(args, net, cands):
     whole list is tokenised on every rank, so a row's padded length does not depend on the world size."""
     import torch
 
-    rank, ws = mdist.world()
     C = len(cands)
-    lo, hi = mdist.shard_range(C, rank, ws) if ws > 1 else (0, C)
+    lo, hi = _my_range(C)
     templates = getattr(args, "templates", None)
     with torch.no_grad():
         if hi <= lo:
@@ -671,17 +647,12 @@ def get_neglabel_score(args, net, loader, bank_info):
     """`--score neglabel`: per sample -(1/G) sum_g S_g, S_g the softmax mass at temperature `args.neg_T` (0.01) of its unit-norm
     feature on the ID prompts against negative group g alone (`net.neglabel_scores`); larger = more OOD.  Sharded and gathered
     like `get_knn_score`; EVERY sample is scored.  Returns a float32 ndarray [len(loader.dataset)]."""
-    import torch
-
     if not hasattr(net, "neglabel_scores"):
         raise TypeError("get_neglabel_score needs a net with neglabel_scores (a NativeCLIP); there is no eager fallback")
     bank, K, G, gs = bank_info["bank"], int(bank_info["K"]), int(bank_info["G"]), int(bank_info["gs"])
     T = float(getattr(args, "neg_T", 0.01))
-    n_total = len(loader.dataset)
-    with torch.no_grad():
-        out = [net.neglabel_scores(_unit_image_features(net, images), bank, K, G, gs, T=T)
-               for images, _labels in _shard_batches(loader, n_total, "neglabel")]
-    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
+    return _score_loader(loader, len(loader.dataset), "neglabel", bank.device,
+                         lambda images: net.neglabel_scores(_unit_image_features(net, images), bank, K, G, gs, T=T))
 
 
 def vim_principal_dim(P, D=0):
@@ -741,7 +712,7 @@ def get_vim_fit(args, net, train_loader, test_labels):
     with torch.no_grad():
         state = net.maha_fit_state(None)
         shard = []
-        for images, _labels in _shard_batches(train_loader, n_total, "vim"):
+        for images, _labels in _shard_batches(train_loader, n_total, _BY_INDEX.format("vim"))[0]:
             f = _unit_image_features(net, images).contiguous()
             net.maha_fit_accumulate(f, state)
             shard.append(f)
@@ -782,17 +753,12 @@ def get_vim_score(args, net, loader, fit):
     unit-norm feature's component in the null space of the training features' principal subspace, scaled to logit units, minus
     the energy of its logits at temperature fit["T"]; larger = more OOD.  Sharded and gathered like `get_knn_score`; EVERY
     sample is scored.  Returns a float32 ndarray [len(loader.dataset)]."""
-    import torch
-
     if not hasattr(net, "vim_scores"):
         raise TypeError("get_vim_score needs a net with vim_scores (a NativeCLIP); there is no eager fallback")
     bank, K = fit["bank"], int(fit["K"])
     T, alpha = float(fit["T"]), float(fit["alpha"])
-    n_total = len(loader.dataset)
-    with torch.no_grad():
-        out = [net.vim_scores(_unit_image_features(net, images), bank, K, T=T, alpha=alpha)
-               for images, _labels in _shard_batches(loader, n_total, "vim")]
-    return _gather_shards(out, n_total, bank.device).cpu().numpy().astype(np.float32)
+    return _score_loader(loader, len(loader.dataset), "vim", bank.device,
+                         lambda images: net.vim_scores(_unit_image_features(net, images), bank, K, T=T, alpha=alpha))
 
 
 def _gather_batch_shards(local, n_total, ws):

@@ -299,6 +299,19 @@ class NativeCLIP:
             raise ValueError(f"Input image size {tuple(pixel_values.shape)} doesn't match model (3x{S}x{S}).")
         return pixel_values.to(device=self.device, dtype=torch.float32).contiguous()
 
+    @staticmethod
+    def _chunks(b, nb):
+        """(start, n) of the chunks of at most nb that b images go through a fixed workspace in."""
+        for s in range(0, b, nb):
+            yield s, min(nb, b - s)
+
+    def _x2_batch(self):
+        """`x2_max_batch` where the split-activation arm exists."""
+        nb = self.x2_max_batch
+        if nb <= 0:
+            raise RuntimeError("the split-activation arm needs an fp16 handle")
+        return nb
+
     # -- the model contract ----------------------------------------------------------------
     def get_image_features(self, pixel_values, normalize: bool = False):
         """[b,3,S,S] fp32 (or [b,S,S,3] uint8) → [b,P] fp32.  With the default `normalize=False` this is
@@ -313,8 +326,7 @@ class NativeCLIP:
         px = self._pixels(pixel_values)
         fmt = 1 if px.dtype == torch.uint8 else 0
         out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        for s in range(0, px.shape[0], self.max_batch):
-            n = min(self.max_batch, px.shape[0] - s)
+        for s, n in self._chunks(px.shape[0], self.max_batch):
             self._check(self._lib.mcm_encode_image_ex(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)),
                                                       out[s:s + n].data_ptr(), _stream_ptr()))
         return out
@@ -388,12 +400,11 @@ class NativeCLIP:
         B, N = int(f.shape[0]), int(bk.shape[0])
         scores = torch.empty(B, device=self.device, dtype=torch.float32)
         topv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32) if return_values else None
-        for s, n, work in self._bank_blocks(B, getattr(self, "_knn_work", None), lambda n, need: self._check_knn(
-                self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, need), n, N, k, splits)):
-            self._knn_work = work
-            self._check(self._lib.mcm_knn_score_features(
+        self._bank_score("_knn_work", B, lambda n, need: self._check_knn(
+            self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, need), n, N, k, splits),
+            lambda s, n, work: self._check(self._lib.mcm_knn_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), N, k, splits, work.data_ptr(), work.numel() * 4,
-                scores[s:s + n].data_ptr(), topv[s:s + n].data_ptr() if return_values else None, _stream_ptr()))
+                scores[s:s + n].data_ptr(), topv[s:s + n].data_ptr() if return_values else None, _stream_ptr())))
         return (scores, topv) if return_values else scores
 
     def _bank_operands(self, features, bank):
@@ -407,20 +418,22 @@ class NativeCLIP:
             raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
         return f, bk
 
-    def _bank_blocks(self, B, work, workspace_bytes):
-        """The B queries of a bank-streamed score in blocks of at most 4096 rows, as (start, n, work): workspace_bytes(n,
-        byref(int64)) asks the library what a block of n needs (and raises where it refuses); `work` is the caller's buffer
-        (or None), replaced by a larger one where it is too small.  The caller keeps what it is handed: one buffer per
-        score, since two scores may be in flight on two streams."""
+    def _bank_score(self, slot, B, ask, launch):
+        """The B queries of a bank-streamed score in blocks of at most 4096 rows: ask(n, byref(int64)) asks the library what a
+        block of n needs (and raises where it refuses), launch(start, n, work) scores the block.  `work` is the buffer kept in
+        the attribute `slot`, replaced by a larger one where it is too small: one buffer per score, since two scores may be in
+        flight on two streams."""
         import torch
 
+        work = getattr(self, slot, None)
         for s in range(0, max(B, 1), 4096):
             n = min(4096, B - s)
             need = ctypes.c_int64(0)
-            workspace_bytes(n, ctypes.byref(need))
+            ask(n, ctypes.byref(need))
             if work is None or work.numel() * 4 < need.value:
                 work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
-            yield s, n, work
+                setattr(self, slot, work)
+            launch(s, n, work)
 
     def _check_knn(self, rc, B, N, k, splits):
         if rc:
@@ -444,13 +457,12 @@ class NativeCLIP:
         B = int(f.shape[0])
         scores = torch.empty(B, device=self.device, dtype=torch.float32)
         grp = torch.empty((B, G), device=self.device, dtype=torch.float32) if return_groups else None
-        for s, n, work in self._bank_blocks(B, getattr(self, "_neg_work", None), lambda n, need: self._check_neglabel(
-                self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, need), n, K, G, gs, T, splits)):
-            self._neg_work = work
-            self._check_neglabel(self._lib.mcm_neglabel_score_features(
+        self._bank_score("_neg_work", B, lambda n, need: self._check_neglabel(
+            self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, need), n, K, G, gs, T, splits),
+            lambda s, n, work: self._check_neglabel(self._lib.mcm_neglabel_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, G, gs, T, splits, work.data_ptr(), work.numel() * 4,
                 scores[s:s + n].data_ptr(), grp[s:s + n].data_ptr() if return_groups else None, _stream_ptr()),
-                n, K, G, gs, T, splits)
+                n, K, G, gs, T, splits))
         return (scores, grp) if return_groups else scores
 
     def _check_neglabel(self, rc, B, K, G, gs, T, splits):
@@ -485,13 +497,12 @@ class NativeCLIP:
         B = int(f.shape[0])
         scores = torch.empty(B, device=self.device, dtype=torch.float32)
         parts = torch.empty((B, 3), device=self.device, dtype=torch.float32) if return_parts else None
-        for s, n, work in self._bank_blocks(B, getattr(self, "_vim_work", None), lambda n, need: self._check_vim(
-                self._lib.mcm_vim_workspace_bytes(self._h, n, K, R, splits, need), n, K, R, T, alpha, splits)):
-            self._vim_work = work
-            self._check_vim(self._lib.mcm_vim_score_features(
+        self._bank_score("_vim_work", B, lambda n, need: self._check_vim(
+            self._lib.mcm_vim_workspace_bytes(self._h, n, K, R, splits, need), n, K, R, T, alpha, splits),
+            lambda s, n, work: self._check_vim(self._lib.mcm_vim_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, R, o.data_ptr() if o is not None else None, T, alpha,
                 splits, work.data_ptr(), work.numel() * 4, scores[s:s + n].data_ptr(),
-                parts[s:s + n].data_ptr() if return_parts else None, _stream_ptr()), n, K, R, T, alpha, splits)
+                parts[s:s + n].data_ptr() if return_parts else None, _stream_ptr()), n, K, R, T, alpha, splits))
         return (scores, parts) if return_parts else scores
 
     def _check_vim(self, rc, B, K, R, T, alpha, splits):
@@ -532,8 +543,7 @@ class NativeCLIP:
         b, R, P = px.shape[0], self.local_rows, self.geo.proj_dim
         glob = torch.empty((b, P), device=self.device, dtype=torch.float32)
         loc = torch.empty((b, R, P), device=self.device, dtype=torch.float32)
-        for s in range(0, b, self.max_batch):
-            n = min(self.max_batch, b - s)
+        for s, n in self._chunks(b, self.max_batch):
             self._check(self._lib.mcm_encode_image_local(self._h, px[s:s + n].data_ptr(), fmt, n, glob[s:s + n].data_ptr(),
                                                          loc[s:s + n].data_ptr(), _stream_ptr()))
         return glob, loc
@@ -583,8 +593,7 @@ class NativeCLIP:
         gs = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
         ls = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
         patch = torch.empty((b, R), device=self.device, dtype=torch.float32) if return_parts else None
-        for s in range(0, b, self.max_batch):
-            n = min(self.max_batch, b - s)
+        for s, n in self._chunks(b, self.max_batch):
             self._check(self._lib.mcm_score_glmcm(
                 self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T), float(lam), out[s:s + n].data_ptr(),
                 gs[s:s + n].data_ptr() if return_parts else None, ls[s:s + n].data_ptr() if return_parts else None,
@@ -666,15 +675,12 @@ class NativeCLIP:
         """`score_images` / `score_images_x2` with the top-k tail (mcm_score_topk), in chunks of the arm's largest batch."""
         import torch
 
-        nb = self.x2_max_batch if x2 else self.max_batch
-        if nb <= 0:
-            raise RuntimeError("the split-activation arm needs an fp16 handle")
+        nb = self._x2_batch() if x2 else self.max_batch
         px = self._pixels(pixel_values)
         fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
         t = self._bank(text_features)
         out, idx, prob = self._topk_out(px.shape[0], topk)
-        for s in range(0, px.shape[0], nb):
-            n = min(nb, px.shape[0] - s)
+        for s, n in self._chunks(px.shape[0], nb):
             self._check(self._lib.mcm_score_topk(self._h, px[s:s + n].data_ptr(), fmt, int(x2), n, t.data_ptr(), t.shape[0],
                                                  float(T), SCORE_KINDS[score], int(topk), out[s:s + n].data_ptr(),
                                                  idx[s:s + n].data_ptr(), prob[s:s + n].data_ptr(), _stream_ptr()))
@@ -718,8 +724,7 @@ class NativeCLIP:
         t = self._bank(text_features)
         if out is None:
             out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
-        for s in range(0, px.shape[0], self.max_batch):
-            n = min(self.max_batch, px.shape[0] - s)
+        for s, n in self._chunks(px.shape[0], self.max_batch):
             self._check(fn(self._h, px[s:s + n].data_ptr(), n, t.data_ptr(), t.shape[0], float(T),
                            SCORE_KINDS[score], out[s:s + n].data_ptr(), _stream_ptr()))
         return out
@@ -743,16 +748,13 @@ class NativeCLIP:
 
         if topk:
             return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=True)
-        nb = self.x2_max_batch
-        if nb <= 0:
-            raise RuntimeError("the split-activation arm needs an fp16 handle")
+        nb = self._x2_batch()
         px = self._pixels(pixel_values)
         fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
         t = self._bank(text_features)
         if out is None:
             out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
-        for s in range(0, px.shape[0], nb):
-            n = min(nb, px.shape[0] - s)
+        for s, n in self._chunks(px.shape[0], nb):
             self._check(self._lib.mcm_score_x2(self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T),
                                                SCORE_KINDS[score], out[s:s + n].data_ptr(), _stream_ptr()))
         return out
@@ -761,14 +763,11 @@ class NativeCLIP:
         """`get_image_features` through the split-activation arm (raw projected features unless `normalize`)."""
         import torch
 
-        nb = self.x2_max_batch
-        if nb <= 0:
-            raise RuntimeError("the split-activation arm needs an fp16 handle")
+        nb = self._x2_batch()
         px = self._pixels(pixel_values)
         fmt = 1 if px.dtype == torch.uint8 else 0
         out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        for s in range(0, px.shape[0], nb):
-            n = min(nb, px.shape[0] - s)
+        for s, n in self._chunks(px.shape[0], nb):
             self._check(self._lib.mcm_encode_image_x2(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)),
                                                       out[s:s + n].data_ptr(), _stream_ptr()))
         return out

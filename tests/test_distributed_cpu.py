@@ -363,3 +363,148 @@ def test_refinement_window_inside_one_rank(ws):
     # the 64 calibration images (one run of 64 here) belong to one shard, the window to the shard that holds index 0.95 n
     assert got[owner_id][5] >= n_win_id and sum(1 for g in got if g[5] > 0) <= 2
     assert sum(1 for g in got if g[6] > 0) == 1            # the OOD window: one owner, everybody else contributes zeros
+
+
+# ---- one sharded walk behind every routine (mcm_amd.detection._shard_batches): each gives at every world size what it gives alone
+
+
+class _LatticeSet(torch.utils.data.Dataset):
+    """Pixels are multiples of 3 in [-12, 12]: every sum the stubs below take — a batch mean included — is exact in any order, so
+    a fit that is all-reduced over the ranks has the bits of the one-rank fit."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(300 + int(i))
+        return 3.0 * torch.randint(-4, 5, (3, 4, 4), generator=g).float(), int(i) % 3
+
+
+class _StubEveryNet(_StubNet):
+    """What the six routines ask of a net, on the first 4 pixel values of an image."""
+
+    def get_image_features(self, pixel_values):
+        return pixel_values.reshape(pixel_values.shape[0], -1)[:, :4].float() + 1.0
+
+    def score_images(self, images, text, T, score, topk=0):
+        s = super().score_images(images, text, T, score)
+        flat = images.reshape(images.shape[0], -1)
+        return (s, flat[:, :topk].to(torch.int32), flat[:, topk:2 * topk].float() / 16) if topk else s
+
+    def knn_scores(self, features, bank, k, splits=0, return_values=False):
+        v = torch.topk(features.double() @ bank.double().T, int(k), dim=1).values
+        return torch.sqrt(torch.clamp(2.0 - 2.0 * v[:, -1], min=0.0)).float()
+
+    def maha_prepare(self, mu, prec):
+        return {"mu": mu.double(), "prec": prec.double()}
+
+    def maha_scores(self, f, st):
+        d = f.double()[:, None, :] - st["mu"][None]
+        return (0.5 * torch.einsum("bcp,pq,bcq->bc", d, st["prec"], d)).min(dim=1).values.float()
+
+    def maha_fit_state(self, shift=None):
+        return {"gram": torch.zeros(4, 4, dtype=torch.float64), "sum": torch.zeros(4, dtype=torch.float64),
+                "shift": shift.float(), "n": 0}
+
+    def maha_fit_accumulate(self, f, state):
+        x = f.double() - state["shift"].double()
+        state["gram"] += x.T @ x
+        state["sum"] += x.sum(dim=0)
+        state["n"] += int(f.shape[0])
+
+
+def _opaque(loader):
+    """`loader` behind an iterable that `shard_loader` cannot split by index."""
+    class Plain:
+        dataset = loader.dataset
+
+        def __len__(self):
+            return len(loader)
+
+        def __iter__(self):
+            return iter(loader)
+
+    return Plain()
+
+
+def _every_walk(n, bs):
+    """{name: array} of the routines that walk a sharded loader, over n lattice samples in batches of bs."""
+    import types as _t
+
+    from mcm_amd import detection as det
+    from mcm_amd.synth import class_names
+
+    args = _t.SimpleNamespace(ckpt="x", model="CLIP", score="MCM", T=1, normalize=False, batch_size=bs, n_cls=3, feat_dim=4,
+                              template_dir=None)
+    net, labels = _StubEveryNet(), class_names(3)
+    loader = torch.utils.data.DataLoader(_LatticeSet(n), batch_size=bs, shuffle=False)
+    out = {"clip": det.get_ood_scores_clip(args, net, loader, labels),
+           "clip/opaque": det.get_ood_scores_clip(args, net, _opaque(loader), labels)}
+    out.update(zip(("pred/scores", "pred/idx", "pred/prob", "pred/labels"), det.get_ood_predictions_clip(args, net, loader, labels, topk=2)))
+    unit = lambda f: f / f.norm(dim=-1, keepdim=True)  # noqa: E731
+    bank = unit(torch.arange(1.0, 21.0).reshape(5, 4))
+    out["knn"] = det.get_knn_score(args, net, loader, bank, 2)
+    mu = torch.arange(12, dtype=torch.float32).reshape(3, 4) / 10
+    out["maha/ood"] = det.get_Mahalanobis_score(args, net, loader, mu, torch.eye(4), in_dist=False)
+    out["fit/mean"], out["fit/precision"] = (t.numpy() for t in det.get_mean_prec_device(args, net, loader))
+    return out
+
+
+def _worker_every_walk(rank, ws, port, n, bs, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(ws), LOCAL_RANK=str(rank))
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", rank=rank, world_size=ws)
+    q.put((rank, _every_walk(n, bs)))
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("ws,n,bs", [(1, 7, 3), (2, 7, 3), (3, 7, 3), (3, 4, 3)])
+def test_every_sharded_walk_equals_single(ws, n, bs):
+    """7 samples in batches of 3 at world sizes 1 (a one-rank group: the collectives run), 2 and 3: a partial last batch, shards
+    that end inside a batch, and for the Mahalanobis OOD rule 6 scored samples; 4 samples on 3 ranks: the last shard is EMPTY.
+    Every rank must return, bit for bit, what one process without a group returns."""
+    want = _every_walk(n, bs)
+    assert want["clip"].shape == (n,) and want["maha/ood"].shape == (n // bs * bs,) and want["pred/idx"].shape == (n, 2)
+    assert want["pred/idx"].dtype == np.int32 and want["pred/labels"].dtype == np.int64 and np.isfinite(want["fit/precision"]).all()
+    np.testing.assert_array_equal(want["clip"], want["clip/opaque"])
+    for rank, got in _run_ranks(_worker_every_walk, ws, (n, bs)):
+        assert sorted(got) == sorted(want)
+        for name in want:
+            assert got[name].dtype == want[name].dtype and got[name].shape == want[name].shape, (rank, name)
+            assert got[name].tobytes() == want[name].tobytes(), (rank, name, got[name], want[name])
+
+
+def test_an_opaque_loader_is_refused_where_it_always_was(monkeypatch):
+    """Under world_size > 1 only `get_ood_scores_clip` walks a loader that cannot be sharded by index; the others refuse it, each
+    in its own words, before anything is iterated."""
+    import types as _t
+
+    from mcm_amd import detection as det
+    from mcm_amd import dist as mdist
+    from mcm_amd.synth import class_names
+
+    args = _t.SimpleNamespace(ckpt="x", model="CLIP", score="MCM", T=1, normalize=False, batch_size=3, n_cls=3, feat_dim=4,
+                              template_dir=None)
+    net = _StubEveryNet()
+
+    class Plain:
+        dataset = _LatticeSet(7)
+
+        def __iter__(self):
+            raise AssertionError("nothing may be iterated")
+
+    monkeypatch.setattr(mdist, "world", lambda: (1, 2))
+    by_index = r"--score {} under world_size > 1 needs a loader that can be sharded by index"
+    with pytest.raises(TypeError, match="get_ood_predictions_clip under world_size > 1 needs a loader with .shard\\(lo, hi\\) or a "
+                                        "torch DataLoader over a map-style dataset"):
+        det.get_ood_predictions_clip(args, net, Plain(), class_names(3), topk=2)
+    with pytest.raises(TypeError, match=by_index.format("knn")):
+        det.get_knn_score(args, net, Plain(), torch.eye(4), 2)
+    with pytest.raises(TypeError, match=by_index.format("maha")):
+        det.get_Mahalanobis_score(args, net, Plain(), torch.zeros(3, 4), torch.eye(4), in_dist=False)
+    with pytest.raises(TypeError, match=by_index.format("maha")):
+        det.get_mean_prec_device(args, net, Plain())
