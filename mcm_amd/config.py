@@ -1,5 +1,5 @@
-"""CLIP geometry for the checkpoints the reference accepts, and the ctypes mirror of
-`mcm_config` (include/mcm.h).
+"""CLIP geometry for the checkpoints the reference accepts, and the structs and constants of
+include/mcm.h as ctypes and Python values (read from the header: mcm_amd/abi.py).
 
 The checkpoint names are the reference's `--CLIP_ckpt` choices
 (eval_ood_detection.py:34-35) and their HF hub ids (utils/train_eval_util.py:19-21);
@@ -11,53 +11,29 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass, asdict, replace
 
-ABI_VERSION = 5
-PREC_BF16 = 0
-PREC_F32 = 1
-PREC_F16 = 2
-DT_F32, DT_F16, DT_BF16 = 0, 1, 2                       # include/mcm.h MCM_DT_*
-WEIGHT_OPERANDS = {"auto": 0, "single": 1, "split": 2}  # include/mcm.h MCM_WEIGHTS_*
-HIDDEN_ACTS = {"quick_gelu": 0, "gelu": 1}              # include/mcm.h MCM_ACT_*: HF `hidden_act` -> mcm_config.*_hidden_act
+from .abi import DEFINES, struct_fields
 
-SCORE_KINDS = {"MCM": 0, "max-logit": 1, "energy": 2, "entropy": 3, "var": 4}
+ABI_VERSION = DEFINES["MCM_ABI_VERSION"]
+PREC_BF16, PREC_F32, PREC_F16 = DEFINES["MCM_PREC_BF16"], DEFINES["MCM_PREC_F32"], DEFINES["MCM_PREC_F16"]
+DT_F32, DT_F16, DT_BF16 = DEFINES["MCM_DT_F32"], DEFINES["MCM_DT_F16"], DEFINES["MCM_DT_BF16"]
+WEIGHT_OPERANDS = {"auto": DEFINES["MCM_WEIGHTS_AUTO"], "single": DEFINES["MCM_WEIGHTS_SINGLE"],
+                   "split": DEFINES["MCM_WEIGHTS_SPLIT"]}
+# HF `hidden_act` -> mcm_config.*_hidden_act
+HIDDEN_ACTS = {"quick_gelu": DEFINES["MCM_ACT_QUICK_GELU"], "gelu": DEFINES["MCM_ACT_GELU"]}
+SCORE_KINDS = {"MCM": DEFINES["MCM_SCORE_MCM"], "max-logit": DEFINES["MCM_SCORE_MAX_LOGIT"], "energy": DEFINES["MCM_SCORE_ENERGY"],
+               "entropy": DEFINES["MCM_SCORE_ENTROPY"], "var": DEFINES["MCM_SCORE_VAR"]}
 
 
 class JpegImage(ctypes.Structure):
-    """Field-for-field mirror of `struct mcm_jpeg_image` in include/mcm.h."""
+    """`struct mcm_jpeg_image` of include/mcm.h."""
 
-    _fields_ = [("status", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
-                ("hs", ctypes.c_int32 * 3), ("vs", ctypes.c_int32 * 3), ("wb", ctypes.c_int32 * 3), ("hb", ctypes.c_int32 * 3),
-                ("coef_off", ctypes.c_int64 * 3)]
+    _fields_ = struct_fields("mcm_jpeg_image")
 
 
 class CConfig(ctypes.Structure):
-    """Field-for-field mirror of `struct mcm_config` in include/mcm.h."""
+    """`struct mcm_config` of include/mcm.h."""
 
-    _fields_ = [
-        ("abi_version", ctypes.c_int32),
-        ("device", ctypes.c_int32),
-        ("precision", ctypes.c_int32),
-        ("image_size", ctypes.c_int32),
-        ("patch_size", ctypes.c_int32),
-        ("v_width", ctypes.c_int32),
-        ("v_heads", ctypes.c_int32),
-        ("v_layers", ctypes.c_int32),
-        ("v_mlp", ctypes.c_int32),
-        ("vocab_size", ctypes.c_int32),
-        ("max_positions", ctypes.c_int32),
-        ("t_width", ctypes.c_int32),
-        ("t_heads", ctypes.c_int32),
-        ("t_layers", ctypes.c_int32),
-        ("t_mlp", ctypes.c_int32),
-        ("proj_dim", ctypes.c_int32),
-        ("ln_eps", ctypes.c_float),
-        ("max_batch", ctypes.c_int32),
-        ("max_prompt_tokens", ctypes.c_int32),
-        ("weight_operands", ctypes.c_int32),
-        ("x2_max_batch", ctypes.c_int32),
-        ("v_hidden_act", ctypes.c_int32),
-        ("t_hidden_act", ctypes.c_int32),
-    ]
+    _fields_ = struct_fields("mcm_config")
 
 
 @dataclass(frozen=True)

@@ -16,6 +16,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import dist as mdist
+from .abi import DEFINES
 from .config import SCORE_KINDS
 from .metrics import get_measures
 from .tokenizer import load_tokenizer
@@ -541,7 +542,7 @@ def get_knn_score(args, net, loader, bank, k):
                          lambda images: net.knn_scores(_unit_image_features(net, images), bank, k))
 
 
-NEG_MAX_GROUPS = 1024  # MCM_NEG_MAX_GROUPS of include/mcm.h
+NEG_MAX_GROUPS = DEFINES["MCM_NEG_MAX_GROUPS"]
 
 
 def clean_negative_words(words, id_names):

@@ -23,17 +23,21 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .config import (ABI_VERSION, CConfig, ClipGeometry, DT_BF16, DT_F16, DT_F32, PREC_BF16, PREC_F16, PREC_F32,
-                     SCORE_KINDS, WEIGHT_OPERANDS, geometry)
+from . import abi
+from .config import (ABI_VERSION, ClipGeometry, DT_BF16, DT_F16, DT_F32, PREC_BF16, PREC_F16, PREC_F32, SCORE_KINDS,
+                     WEIGHT_OPERANDS, geometry)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmcm_hip.so")
 # the same sources built with -DMCM_HARNESS: A/B kernel arms + mcm_debug_* switches; tests and tools only
 HARNESS_LIB_PATH = os.path.join(_HERE, "libmcm_hip_harness.so")
-KERNEL_CLASSES = ["patchify", "gemm", "layernorm", "attention", "pool_project", "score", "embed",
-                  "gemm_qkv", "gemm_outproj", "gemm_fc1", "gemm_fc2"]  # gemm_*: sub-classes of "gemm" (MCM_KC_GEMM_*)
-
-TOPK_MAX = 8  # include/mcm.h MCM_TOPK_MAX: concepts the top-k scoring tail returns per image
+# what libmcm_hip.so exports, and what only the harness library does: the declarations of include/mcm.h
+EXPORTED_SYMBOLS = list(abi.PROTOTYPES)
+HARNESS_ONLY_SYMBOLS = list(abi.HARNESS_PROTOTYPES)
+# MCM_KC_* in the order of mcm_profile_read's arrays, lower-cased; gemm_*: sub-classes of "gemm" (MCM_KC_GEMM_*)
+KERNEL_CLASSES = [name[len("MCM_KC_"):].lower() for name in sorted(abi.DEFINES, key=abi.DEFINES.get)
+                  if name.startswith("MCM_KC_") and name != "MCM_KC_COUNT"]
+TOPK_MAX = abi.DEFINES["MCM_TOPK_MAX"]  # concepts the top-k scoring tail returns per image
 
 _libs = {}
 
@@ -61,146 +65,11 @@ def load_library(harness: bool = False):
         import torch  # noqa: F401
     except ImportError:
         pass
-    L = ctypes.CDLL(path)
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    L.mcm_abi_version.restype = i32
-    L.mcm_create.argtypes = [ctypes.POINTER(CConfig), ctypes.POINTER(vp)]
-    L.mcm_destroy.argtypes = [vp]
-    L.mcm_destroy.restype = None
-    L.mcm_last_error.argtypes = [vp]
-    L.mcm_last_error.restype = ctypes.c_char_p
-    L.mcm_set_weight.argtypes = [vp, ctypes.c_char_p, vp, i32, ctypes.POINTER(ctypes.c_int64), i32]
-    L.mcm_weights_operand_exact.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i32)]
-    L.mcm_finalize_weights.argtypes = [vp]
-    L.mcm_encode_text.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.mcm_encode_image.argtypes = [vp, vp, i32, vp, vp]
-    L.mcm_score_features.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
-    L.mcm_score.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
-    L.mcm_score_features_topk.argtypes = [vp, vp, i32, vp, i32, f32, i32, i32, vp, vp, vp, vp]
-    L.mcm_score_topk.argtypes = [vp, vp, i32, i32, i32, vp, i32, f32, i32, i32, vp, vp, vp, vp]
-    L.mcm_profile_enable.argtypes = [vp, i32]
-    L.mcm_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double),
-                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]
-    L.mcm_op_linear.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mcm_op_linear_ex.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.mcm_op_split_weight.argtypes = [vp, i32, vp, i32, i32, vp, vp]
-    L.mcm_op_layernorm.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, f32, i32, vp]
-    L.mcm_op_attention.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp]
-    L.mcm_op_layernorm_split.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp]
-    L.mcm_op_attention_split.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    L.mcm_x2_max_batch.argtypes = [vp]
-    L.mcm_x2_max_batch.restype = i32
-    L.mcm_kernel_faults.argtypes = [vp]
-    L.mcm_kernel_faults.restype = i32
-    L.mcm_encode_image_x2.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.mcm_score_x2.argtypes = [vp, vp, i32, i32, vp, i32, f32, i32, vp, vp]
-    if harness:
-        L.mcm_debug_gemm_variant.argtypes = [i32]
-        L.mcm_debug_op_act.argtypes = [vp, i32, vp, vp, ctypes.c_int64, vp]
-        L.mcm_debug_attention_variant.argtypes = [i32]
-        L.mcm_debug_attn_spin_budget.argtypes = [ctypes.c_int64]
-        L.mcm_debug_clear_faults.argtypes = [vp]
-        L.mcm_debug_qkv_chunks.argtypes = [i32]
-        L.mcm_debug_ln_fold.argtypes = [i32]
-        L.mcm_debug_qkv_head_major.argtypes = [i32]
-        L.mcm_debug_ln_tail.argtypes = [i32]
-        L.mcm_debug_ln_cluster.argtypes = [i32]
-        L.mcm_debug_ln_cluster_spin.argtypes = [i32]
-        L.mcm_debug_ln_row.argtypes = [i32]
-        L.mcm_debug_ln_cluster_deferred.argtypes = [vp, vp]
-        L.mcm_debug_ln_tail_timeouts.argtypes = [vp, vp]
-        L.mcm_debug_gemm_dbg.argtypes = [i32]
-        L.mcm_debug_nsplit.argtypes = [i32]
-        L.mcm_debug_gemm_group_n.argtypes = [i32]
-        L.mcm_debug_patch_fold.argtypes = [i32]
-        L.mcm_debug_resize_fused_only.argtypes = [i32]
-        L.mcm_debug_persistent_grid.argtypes = [i32]
-        L.mcm_debug_op_attention.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-        L.mcm_debug_op_attention_split.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-        L.mcm_debug_op_attention_hd.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-        L.mcm_debug_op_attention_split_hd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-        L.mcm_debug_vision_front.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.mcm_debug_op_pool_project.argtypes = [vp, vp, ctypes.c_int64, vp, i32, i32, i32, vp, vp, f32, vp, i32, vp, i32, vp]
-        L.mcm_debug_op_text_embed.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]
-        L.mcm_debug_op_text_embed_ctx.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, i32, vp]
-    L.mcm_encode_image_u8.argtypes = [vp, vp, i32, vp, vp]
-    L.mcm_score_u8.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
-    L.mcm_reduce_bank.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.mcm_resize_crop_u8.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, vp]
-    L.mcm_jpeg_reconstruct.argtypes = [vp, vp, vp, vp, i32, vp, ctypes.POINTER(ctypes.c_int64), vp]
-    L.mcm_jpeg_entropy_decode.argtypes = [ctypes.POINTER(ctypes.c_char_p), i32, vp, ctypes.c_int64, vp, vp, i32,
-                                          ctypes.POINTER(ctypes.c_int64)]
-    L.mcm_pack_u8.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), i32, vp,
-                              ctypes.c_int64, i32]
-    L.mcm_tokenizer_create.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(vp)]
-    L.mcm_tokenizer_destroy.argtypes = [vp]
-    L.mcm_tokenizer_destroy.restype = None
-    L.mcm_tokenizer_last_error.argtypes = [vp]
-    L.mcm_tokenizer_last_error.restype = ctypes.c_char_p
-    L.mcm_tokenizer_vocab_size.argtypes = [vp]
-    L.mcm_tokenizer_vocab_size.restype = i32
-    L.mcm_tokenizer_encode.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32, i32, vp, vp, ctypes.POINTER(i32)]
-    L.mcm_encode_image_raw.argtypes = [vp, vp, i32, vp, vp]
-    L.mcm_encode_image_ex.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.mcm_encode_text_ex.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.mcm_encode_text_ctx.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp]
-    L.mcm_score_histogram.argtypes = [vp, vp, ctypes.c_int64, vp, i32, vp, vp]
-    L.mcm_maha_prepare.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-    L.mcm_maha_score_features.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
-    L.mcm_maha_fit_accumulate.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    L.mcm_knn_workspace_bytes.argtypes = [vp, i32, ctypes.c_int64, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-    L.mcm_knn_score_features.argtypes = [vp, vp, i32, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp, vp, vp]
-    L.mcm_neglabel_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-    L.mcm_neglabel_score_features.argtypes = [vp, vp, i32, vp, i32, i32, i32, ctypes.c_float, i32, vp, ctypes.c_int64, vp, vp, vp]
-    L.mcm_vim_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-    L.mcm_vim_score_features.argtypes = [vp, vp, i32, vp, i32, i32, vp, ctypes.c_float, ctypes.c_float, i32, vp, ctypes.c_int64,
-                                         vp, vp, vp]
-    L.mcm_local_workspace_bytes.argtypes = [vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-    L.mcm_local_score_features.argtypes = [vp, vp, i32, i32, vp, i32, ctypes.c_float, vp, ctypes.c_int64, vp, vp, vp]
-    L.mcm_encode_image_local.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    L.mcm_score_glmcm.argtypes = [vp, vp, i32, i32, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, vp]
-    L.mcm_measures.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i32, ctypes.c_double,
-                               ctypes.POINTER(ctypes.c_double), vp]
-    L.mcm_saturation_check.argtypes = [vp, i32]
-    L.mcm_saturation_count.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_uint64), vp]
+    L = abi.declare(ctypes.CDLL(path), harness=harness)
     if L.mcm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {L.mcm_abi_version()}, this package speaks {ABI_VERSION} — rebuild (make -C mcm_amd/csrc)")
     _libs[harness] = L
     return L
-
-
-EXPORTED_SYMBOLS = [
-    "mcm_abi_version", "mcm_create", "mcm_destroy", "mcm_last_error", "mcm_set_weight",
-    "mcm_finalize_weights", "mcm_encode_text", "mcm_encode_image", "mcm_score_features",
-    "mcm_score", "mcm_profile_enable", "mcm_profile_read", "mcm_op_linear", "mcm_op_layernorm",
-    "mcm_op_attention", "mcm_encode_image_u8", "mcm_score_u8",
-    "mcm_reduce_bank", "mcm_measures", "mcm_resize_crop_u8", "mcm_tokenizer_create",
-    "mcm_tokenizer_destroy", "mcm_tokenizer_last_error", "mcm_tokenizer_vocab_size", "mcm_tokenizer_encode",
-    "mcm_encode_image_raw", "mcm_maha_prepare", "mcm_maha_score_features",
-    "mcm_encode_image_ex", "mcm_encode_text_ex", "mcm_score_histogram",
-    "mcm_saturation_check", "mcm_saturation_count",
-    "mcm_weights_operand_exact", "mcm_op_linear_ex", "mcm_op_split_weight", "mcm_pack_u8",
-    "mcm_jpeg_entropy_decode", "mcm_jpeg_reconstruct",
-    "mcm_x2_max_batch", "mcm_encode_image_x2", "mcm_score_x2", "mcm_op_layernorm_split", "mcm_op_attention_split",
-    "mcm_kernel_faults",
-    "mcm_score_features_topk", "mcm_score_topk",
-    "mcm_maha_fit_accumulate",
-    "mcm_knn_workspace_bytes", "mcm_knn_score_features",
-    "mcm_neglabel_workspace_bytes", "mcm_neglabel_score_features",
-    "mcm_local_workspace_bytes", "mcm_local_score_features", "mcm_encode_image_local", "mcm_score_glmcm",
-    "mcm_vim_workspace_bytes", "mcm_vim_score_features",
-    "mcm_encode_text_ctx",
-]
-HARNESS_ONLY_SYMBOLS = ["mcm_debug_gemm_variant", "mcm_debug_attention_variant", "mcm_debug_qkv_chunks",
-                        "mcm_debug_gemm_dbg", "mcm_debug_ln_fold", "mcm_debug_qkv_head_major",
-                        "mcm_debug_ln_tail", "mcm_debug_ln_tail_timeouts", "mcm_debug_nsplit",
-                        "mcm_debug_gemm_group_n", "mcm_debug_patch_fold", "mcm_debug_resize_fused_only",
-                        "mcm_debug_persistent_grid", "mcm_debug_op_attention", "mcm_debug_attn_spin_budget",
-                        "mcm_debug_clear_faults", "mcm_debug_ln_cluster", "mcm_debug_ln_cluster_spin",
-                        "mcm_debug_ln_cluster_deferred", "mcm_debug_ln_row", "mcm_debug_op_attention_split",
-                        "mcm_debug_vision_front", "mcm_debug_op_pool_project", "mcm_debug_op_text_embed",
-                        "mcm_debug_op_act", "mcm_debug_op_attention_hd", "mcm_debug_op_attention_split_hd",
-                        "mcm_debug_op_text_embed_ctx"]
 
 
 def _stream_ptr():

@@ -9,7 +9,7 @@ import types
 import numpy as np
 import pytest
 
-from mcm_amd import config as cfgmod
+from mcm_amd import abi, config as cfgmod
 from mcm_amd.engine import EXPORTED_SYMBOLS, HARNESS_LIB_PATH, HARNESS_ONLY_SYMBOLS, LIB_PATH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +21,7 @@ def lib():
         import __graft_entry__ as g
 
         g.build()
-    return ctypes.CDLL(LIB_PATH)
+    return abi.declare(ctypes.CDLL(LIB_PATH))
 
 
 def test_library_exports_every_declared_symbol(lib):
@@ -33,7 +33,6 @@ def test_library_exports_every_declared_symbol(lib):
     assert declared == set(EXPORTED_SYMBOLS), declared ^ set(EXPORTED_SYMBOLS)
     for sym in declared:
         assert getattr(lib, sym) is not None
-    lib.mcm_abi_version.restype = ctypes.c_int32
     assert lib.mcm_abi_version() == cfgmod.ABI_VERSION
     # the A/B switches exist in the harness library only: the shipped one does not export them
     debug = set(re.findall(r"\b(mcm_[a-z0-9_]+)\s*\(", harness_part))
@@ -54,9 +53,6 @@ def test_config_struct_matches_header():
 
 
 def test_create_rejects_bad_config_without_gpu(lib):
-    lib.mcm_create.argtypes = [ctypes.POINTER(cfgmod.CConfig), ctypes.POINTER(ctypes.c_void_p)]
-    lib.mcm_last_error.restype = ctypes.c_char_p
-    lib.mcm_last_error.argtypes = [ctypes.c_void_p]
     h = ctypes.c_void_p()
     bad = cfgmod.geometry("ViT-B/16").to_c()
     bad.abi_version = 99
@@ -180,9 +176,8 @@ def test_native_image_packing_equals_a_python_copy():
 
     from mcm_amd.engine import LIB_PATH
 
-    L = ctypes.CDLL(LIB_PATH)
+    L = abi.declare(ctypes.CDLL(LIB_PATH), names=["mcm_pack_u8"])
     vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    L.mcm_pack_u8.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.c_int32, vp, i64, ctypes.c_int32]
     rng = np.random.default_rng(3)
     shapes = [(int(rng.integers(1, 400)), int(rng.integers(1, 500)), 3) for _ in range(97)] + [(1200, 1600, 3), (1, 1, 3)]
     imgs = [rng.integers(0, 256, size=s, dtype=np.uint8) for s in shapes]

@@ -20,22 +20,9 @@ SECTION_8B = ["mcm_create", "mcm_set_weight", "mcm_encode_text", "mcm_encode_ima
 def lib():
     if not os.path.exists(LIB):
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "libmcm_cpu.so"], check=True, capture_output=True)
-    L = ctypes.CDLL(LIB)
-    from mcm_amd.config import CConfig
+    from mcm_amd import abi
 
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    L.mcm_create.argtypes = [ctypes.POINTER(CConfig), ctypes.POINTER(vp)]
-    L.mcm_destroy.argtypes = [vp]
-    L.mcm_destroy.restype = None
-    L.mcm_last_error.argtypes = [vp]
-    L.mcm_last_error.restype = ctypes.c_char_p
-    L.mcm_set_weight.argtypes = [vp, ctypes.c_char_p, vp, i32, ctypes.POINTER(ctypes.c_int64), i32]
-    L.mcm_finalize_weights.argtypes = [vp]
-    L.mcm_encode_text.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.mcm_encode_image.argtypes = [vp, vp, i32, vp, vp]
-    L.mcm_score.argtypes = [vp, vp, i32, vp, i32, f32, i32, vp, vp]
-    L.mcm_weights_operand_exact.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i32)]
-    return L
+    return abi.declare(ctypes.CDLL(LIB), names=SECTION_8B + ["mcm_finalize_weights", "mcm_weights_operand_exact"])
 
 
 def test_the_twin_exports_what_section_8b_lists_and_so_does_the_product_library(lib):

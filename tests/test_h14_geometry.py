@@ -122,11 +122,9 @@ def lib():
         import __graft_entry__ as g
 
         g.build()
-    L = ctypes.CDLL(LIB_PATH)
-    L.mcm_create.argtypes = [ctypes.POINTER(cfgmod.CConfig), ctypes.POINTER(ctypes.c_void_p)]
-    L.mcm_last_error.restype = ctypes.c_char_p
-    L.mcm_last_error.argtypes = [ctypes.c_void_p]
-    return L
+    from mcm_amd import abi
+
+    return abi.declare(ctypes.CDLL(LIB_PATH), names=["mcm_create", "mcm_last_error"])
 
 
 def test_create_still_refuses_other_head_widths_without_gpu(lib):
