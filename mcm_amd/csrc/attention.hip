@@ -754,23 +754,16 @@ unsigned int g_ps_spin_budget = PS_SPIN_BUDGET;   // mcm_debug_attn_spin_budget:
 template <int PREC, int NT, int NFULL, int NLD>
 hipError_t launch_ps(const void* qkv, void* out, int nseq, int L, int heads, int qrows, hipStream_t s, int rev, unsigned int* fault) {
   constexpr int lds = 3 * 2 * NT * 16 * 128 + 64;
-  static PerDeviceFlag attr_set;
   const int cus = device_cu_count();
   if (cus <= 0) return hipErrorInvalidDevice;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_ps_kernel<PREC, NT, NFULL, NLD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
   const int njobs = nseq * heads;
 #ifdef MCM_HARNESS
   const unsigned int budget = g_ps_spin_budget;
 #else
   const unsigned int budget = PS_SPIN_BUDGET;
 #endif
-  hipLaunchKernelGGL((attn_ps_kernel<PREC, NT, NFULL, NLD>), dim3(min(cus, njobs)), dim3(1024), lds, s, (const uint16_t*)qkv,
-                     (uint16_t*)out, L, heads, qrows, njobs, rev & 1, budget, fault);
-  return hipGetLastError();
+  return launch_lds<attn_ps_kernel<PREC, NT, NFULL, NLD>, lds>(dim3(min(cus, njobs)), dim3(1024), lds, s, (const uint16_t*)qkv,
+                                                               (uint16_t*)out, L, heads, qrows, njobs, rev & 1, budget, fault);
 }
 
 // ---- fp32 parity arm -------------------------------------------------------------------
@@ -937,15 +930,8 @@ template <int NT, int NW>
 hipError_t launch_f32_mfma(const void* qkv, void* out, int nseq, int L, int heads, int qrows, hipStream_t s) {
   constexpr int lds = NT * 16 * 68 * 2 * (int)sizeof(float);
   static_assert(lds <= 160 * 1024, "K and V of one head must fit the LDS");
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_f32_mfma_kernel<NT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((attn_f32_mfma_kernel<NT, NW>), dim3(nseq * heads), dim3(NW * 64), lds, s, (const float*)qkv, (float*)out, L,
-                     heads, qrows);
-  return hipGetLastError();
+  return launch_lds<attn_f32_mfma_kernel<NT, NW>, lds>(dim3(nseq * heads), dim3(NW * 64), lds, s, (const float*)qkv, (float*)out,
+                                                       L, heads, qrows);
 }
 
 #ifdef MCM_HARNESS
@@ -953,23 +939,10 @@ template <int PREC, int LP>
 hipError_t launch_bf16(const void* qkv, void* out, int nseq, int L, int heads, bool causal,
                        int qrows, hipStream_t s, int rev) {
   constexpr int lds = LP * 128 + 64 * vt_stride(LP);
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bf16_kernel<PREC, LP, false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)attn_bf16_kernel<PREC, LP, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
+  const dim3 grid(nseq * heads), block(256);
   if (causal)
-    hipLaunchKernelGGL((attn_bf16_kernel<PREC, LP, true>), dim3(nseq * heads), dim3(256), lds, s,
-                       (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev);
-  else
-    hipLaunchKernelGGL((attn_bf16_kernel<PREC, LP, false>), dim3(nseq * heads), dim3(256), lds, s,
-                       (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev);
-  return hipGetLastError();
+    return launch_lds<attn_bf16_kernel<PREC, LP, true>, lds>(grid, block, lds, s, (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev);
+  return launch_lds<attn_bf16_kernel<PREC, LP, false>, lds>(grid, block, lds, s, (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev);
 }
 
 #endif
@@ -983,31 +956,15 @@ template <int PREC, int NT, int NW, int OCC, bool X2 = false, int NFULL = 0>
 hipError_t launch_tr(const void* qkv, void* out, int nseq, int L, int heads, bool causal, int qrows,
                      hipStream_t s, int rev, int hm) {
   constexpr int lds = NT * 16 * 128 * (X2 ? 4 : 2);
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_tr_kernel<PREC, NT, false, NW, OCC, X2, NFULL>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if constexpr (!X2) {
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)attn_tr_kernel<PREC, NT, true, NW, OCC, X2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
+  const dim3 grid(nseq * heads), block(NW * 64);
+  const uint16_t* in = (const uint16_t*)qkv;
+  uint16_t* o = (uint16_t*)out;
   if constexpr (X2) {  // (the vision tower only: no causal form)
     if (causal) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((attn_tr_kernel<PREC, NT, false, NW, OCC, true, NFULL>), dim3(nseq * heads), dim3(NW * 64), lds, s,
-                       (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev, hm);
-    return hipGetLastError();
+    return launch_lds<attn_tr_kernel<PREC, NT, false, NW, OCC, true, NFULL>, lds>(grid, block, lds, s, in, o, L, heads, qrows, rev, hm);
   } else {
-  if (causal)
-    hipLaunchKernelGGL((attn_tr_kernel<PREC, NT, true, NW, OCC>), dim3(nseq * heads), dim3(NW * 64), lds, s,
-                       (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev, hm);
-  else
-    hipLaunchKernelGGL((attn_tr_kernel<PREC, NT, false, NW, OCC, false, NFULL>), dim3(nseq * heads), dim3(NW * 64), lds, s,
-                       (const uint16_t*)qkv, (uint16_t*)out, L, heads, qrows, rev, hm);
-  return hipGetLastError();
+    if (causal) return launch_lds<attn_tr_kernel<PREC, NT, true, NW, OCC>, lds>(grid, block, lds, s, in, o, L, heads, qrows, rev, hm);
+    return launch_lds<attn_tr_kernel<PREC, NT, false, NW, OCC, false, NFULL>, lds>(grid, block, lds, s, in, o, L, heads, qrows, rev, hm);
   }
 }
 
@@ -1814,68 +1771,62 @@ hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int 
   if (nseq <= 0 || L <= 0 || heads <= 0) return hipErrorInvalidValue;
   if (head_dim != 64 && head_dim != H80) return hipErrorInvalidValue;
   if (qrows <= 0 || qrows > L) qrows = L;
+  const int rev = reverse ? 1 : 0;
   // head_dim 80 (ViT-H/14's vision tower): the streaming family at every length; bidirectional, row-major qkv only
   if (head_dim == H80) {
     if (causal || hm || L > LONG_MAX_L) return hipErrorInvalidValue;
-    const int rv = reverse ? 1 : 0;
     if (split) {  // (a split row is whole 64-column blocks: heads a multiple of 4)
       if (prec != MCM_PREC_F16 || (heads * H80) % 64) return hipErrorInvalidValue;
-      return launch_hd80<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, rv);
+      return launch_hd80<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, rev);
     }
-    if (prec == MCM_PREC_F16) return launch_hd80<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, rv);
-    if (prec == MCM_PREC_BF16) return launch_hd80<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, rv);
-    if (prec == MCM_PREC_F32) return launch_hd80<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, rv);
+    if (prec == MCM_PREC_F16) return launch_hd80<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, rev);
+    if (prec == MCM_PREC_BF16) return launch_hd80<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, rev);
+    if (prec == MCM_PREC_F32) return launch_hd80<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, rev);
     return hipErrorInvalidValue;
   }
+  // head-major qkv, the same for every family below: 16-bit modes, the array covers the launch; harness library only.
+  // (Nothing is launched on a refusal, so it does not matter that the checks of a family come after these.)
+  if (hm && (prec == MCM_PREC_F32 || (int64_t)hm < (int64_t)nseq * L)) return hipErrorInvalidValue;
+#ifndef MCM_HARNESS
+  if (hm) return hipErrorInvalidValue;
+#endif
   // Bidirectional problems past 18 key tiles (L > 288): the streaming kernels (K / V through LDS, online softmax), every mode.
   // Everything at L <= 288, and causal attention at any length, keeps the kernels below.
   if (!causal && (L + 15) / 16 > 18) {
     if (L > LONG_MAX_L) return hipErrorInvalidValue;
     if (split) {
       if (prec != MCM_PREC_F16 || hm) return hipErrorInvalidValue;
-      return launch_long<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, 0);
+      return launch_long<MCM_PREC_F16, true>(qkv, out, nseq, L, heads, qrows, s, rev, 0);
     }
-    if (hm && (prec == MCM_PREC_F32 || (int64_t)hm < (int64_t)nseq * L)) return hipErrorInvalidValue;
-#ifndef MCM_HARNESS
-    if (hm) return hipErrorInvalidValue;  // head-major qkv: harness library only
-#endif
-    if (prec == MCM_PREC_F16) return launch_long<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, hm);
-    if (prec == MCM_PREC_BF16) return launch_long<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, hm);
-    if (prec == MCM_PREC_F32) return launch_long<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0, 0);
+    if (prec == MCM_PREC_F16) return launch_long<MCM_PREC_F16, false>(qkv, out, nseq, L, heads, qrows, s, rev, hm);
+    if (prec == MCM_PREC_BF16) return launch_long<MCM_PREC_BF16, false>(qkv, out, nseq, L, heads, qrows, s, rev, hm);
+    if (prec == MCM_PREC_F32) return launch_long<MCM_PREC_F32, false>(qkv, out, nseq, L, heads, qrows, s, rev, 0);
     return hipErrorInvalidValue;
   }
   if (split) {  // split images in and out (GemmArgs::xsplit): fp16, bidirectional, row-major
     if (prec != MCM_PREC_F16 || causal || hm) return hipErrorInvalidValue;
-    return launch_tr_x2(qkv, out, nseq, L, heads, qrows, s, reverse ? 1 : 0);
+    return launch_tr_x2(qkv, out, nseq, L, heads, qrows, s, rev);
   }
-  if (hm && (prec == MCM_PREC_F32 || (int64_t)hm < (int64_t)nseq * L)) return hipErrorInvalidValue;
-#ifndef MCM_HARNESS
-  if (hm) return hipErrorInvalidValue;  // head-major qkv: harness library only
-#endif
-#ifdef MCM_HARNESS
-  if (hm && g_attn_variant == 0) return hipErrorInvalidValue;  // the round-1 kernel reads row-major qkv only
-#endif
 #ifdef MCM_HARNESS
   if (prec != MCM_PREC_F32 && g_attn_variant == 0) {
+    if (hm) return hipErrorInvalidValue;  // the round-1 kernel reads row-major qkv only
 #define MCM_ATTN_BY_LP(P)                                                                      \
-  do {                                                                                          \
-    if (L <= 32) return launch_bf16<P, 32>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);         \
-    if (L <= 64) return launch_bf16<P, 64>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);         \
-    if (L <= 96) return launch_bf16<P, 96>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);         \
-    if (L <= 128) return launch_bf16<P, 128>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);       \
-    if (L <= 224) return launch_bf16<P, 224>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);       \
-    if (L <= 288) return launch_bf16<P, 288>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0);       \
-    return hipErrorInvalidValue;                                                                \
+  do {                                                                                         \
+    if (L <= 32) return launch_bf16<P, 32>(qkv, out, nseq, L, heads, causal, qrows, s, rev);   \
+    if (L <= 64) return launch_bf16<P, 64>(qkv, out, nseq, L, heads, causal, qrows, s, rev);   \
+    if (L <= 96) return launch_bf16<P, 96>(qkv, out, nseq, L, heads, causal, qrows, s, rev);   \
+    if (L <= 128) return launch_bf16<P, 128>(qkv, out, nseq, L, heads, causal, qrows, s, rev); \
+    if (L <= 224) return launch_bf16<P, 224>(qkv, out, nseq, L, heads, causal, qrows, s, rev); \
+    if (L <= 288) return launch_bf16<P, 288>(qkv, out, nseq, L, heads, causal, qrows, s, rev); \
+    return hipErrorInvalidValue;                                                               \
   } while (0)
     if (prec == MCM_PREC_F16) MCM_ATTN_BY_LP(MCM_PREC_F16);
     MCM_ATTN_BY_LP(MCM_PREC_BF16);
 #undef MCM_ATTN_BY_LP
   }
 #endif
-  if (prec == MCM_PREC_F16)
-    return launch_tr_by_tiles<MCM_PREC_F16>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0, hm, fault);
-  if (prec == MCM_PREC_BF16)
-    return launch_tr_by_tiles<MCM_PREC_BF16>(qkv, out, nseq, L, heads, causal, qrows, s, reverse ? 1 : 0, hm, fault);
+  if (prec == MCM_PREC_F16) return launch_tr_by_tiles<MCM_PREC_F16>(qkv, out, nseq, L, heads, causal, qrows, s, rev, hm, fault);
+  if (prec == MCM_PREC_BF16) return launch_tr_by_tiles<MCM_PREC_BF16>(qkv, out, nseq, L, heads, causal, qrows, s, rev, hm, fault);
   if (!causal) {  // the vision tower's form: fp32 MFMAs (attn_f32_mfma_kernel); the causal text tower keeps the VALU kernel
     const int nt = (L + 15) / 16;
 #define MCM_F32A(N, W) \
@@ -1884,22 +1835,7 @@ hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int 
 #undef MCM_F32A
   }
   const int lds = (L * 65 + L * 64 + 4 * 64 + 4 * L) * (int)sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_f32_kernel<false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)attn_f32_kernel<true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  if (causal)
-    hipLaunchKernelGGL(attn_f32_kernel<true>, dim3(nseq * heads), dim3(256), lds, s,
-                       (const float*)qkv, (float*)out, L, heads, qrows);
-  else
-    hipLaunchKernelGGL(attn_f32_kernel<false>, dim3(nseq * heads), dim3(256), lds, s,
-                       (const float*)qkv, (float*)out, L, heads, qrows);
-  return hipGetLastError();
+  const dim3 grid(nseq * heads), block(256);
+  if (causal) return launch_lds<attn_f32_kernel<true>, 160 * 1024>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
+  return launch_lds<attn_f32_kernel<false>, 160 * 1024>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
 }

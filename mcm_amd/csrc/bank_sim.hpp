@@ -161,14 +161,6 @@ __device__ __forceinline__ double lse_merge(int s0, int s1, double inv_t, float&
   return tot;
 }
 
-// raises a kernel's dynamic-LDS limit on the current device, once per device (`done`: a static of the launcher)
-inline hipError_t lds_limit_once(PerDeviceFlag& done, const void* kernel, int bytes) {
-  if (done.get()) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) done.set();
-  return e;
-}
-
 inline unsigned query_tiles(int B) { return (unsigned)(((int64_t)B + Q - 1) / Q); }
 }  // namespace bank_sim
 

@@ -6,14 +6,34 @@
 
 #include "../../include/mcm.h"
 
-// hipFuncSetAttribute acts on the CURRENT device's copy of a kernel: a launcher's "already raised the dynamic-LDS limit"
-// flag is kept per device, so that a process holding handles on two devices sets it on both.
+// hipFuncSetAttribute acts on the CURRENT device's copy of a kernel: the "already raised the dynamic-LDS limit" flag is
+// kept per device, so that a process holding handles on two devices sets it on both.
 struct PerDeviceFlag {
   bool done[64] = {};
   static int dev() { int d = 0; return hipGetDevice(&d) == hipSuccess && d >= 0 && d < 64 ? d : -1; }
   bool get() const { const int d = dev(); return d >= 0 && done[d]; }
   void set() { const int d = dev(); if (d >= 0) done[d] = true; }
 };
+// The one place that rule lives: every kernel with dynamic LDS is launched through launch_lds.  The flag belongs to the
+// kernel instantiation (the template argument), not to whichever function launches it.
+// lds_limit: raises Kernel's dynamic-LDS limit to LIMIT bytes on the current device, once per device.
+template <auto Kernel, int LIMIT>
+hipError_t lds_limit() {
+  static PerDeviceFlag done;
+  if (done.get()) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LIMIT);
+  if (e == hipSuccess) done.set();
+  return e;
+}
+// launch_lds: refuses lds > LIMIT, raises the limit, launches, returns the launch's status
+template <auto Kernel, int LIMIT, class... A>
+hipError_t launch_lds(dim3 grid, dim3 block, int lds, hipStream_t s, const A&... args) {
+  if (lds > LIMIT) return hipErrorInvalidValue;
+  const hipError_t e = lds_limit<Kernel, LIMIT>();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
 
 // CUs of the CURRENT device, cached per device (a process may hold handles on several devices, and a partitioned or
 // CU-masked lease reports fewer than 256): the grid of every persistent kernel and the size policies that depend on it

@@ -1282,59 +1282,28 @@ int persistent_grid() {
 
 template <int PREC, int EPI>
 hipError_t launch_tile(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tile_kernel<PREC, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, tile::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
   const int nbn = (a.N + tile::BN - 1) / tile::BN, nbm = (a.M + tile::BM - 1) / tile::BM;
-  hipLaunchKernelGGL((gemm_tile_kernel<PREC, EPI>), dim3(nbn * nbm), dim3(256), tile::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<gemm_tile_kernel<PREC, EPI>, tile::LDS_BYTES>(dim3(nbn * nbm), dim3(256), tile::LDS_BYTES, s, a);
 }
 
 template <int PREC, int EPI>
 hipError_t launch_tile64(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tile64_kernel<PREC, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, tile64::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
   const int nbn = (a.N + tile64::BN - 1) / tile64::BN, nbm = (a.M + tile64::BM - 1) / tile64::BM;
-  hipLaunchKernelGGL((gemm_tile64_kernel<PREC, EPI>), dim3(nbn * nbm), dim3(256), tile64::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<gemm_tile64_kernel<PREC, EPI>, tile64::LDS_BYTES>(dim3(nbn * nbm), dim3(256), tile64::LDS_BYTES, s, a);
 }
 
 template <int PREC, int EPI, bool CS, bool PXF = false>
 hipError_t launch_p256(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_p256_kernel<PREC, EPI, CS, PXF>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, p256::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((gemm_p256_kernel<PREC, EPI, CS, PXF>), dim3(persistent_grid()), dim3(512), p256::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<gemm_p256_kernel<PREC, EPI, CS, PXF>, p256::LDS_BYTES>(dim3(persistent_grid()), dim3(512), p256::LDS_BYTES, s, a);
 }
 
 template <int PREC, int EPI>
 hipError_t launch_pp(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_pp_kernel<PREC, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, p256::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((gemm_pp_kernel<PREC, EPI>), dim3(persistent_grid()), dim3(512), p256::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<gemm_pp_kernel<PREC, EPI>, p256::LDS_BYTES>(dim3(persistent_grid()), dim3(512), p256::LDS_BYTES, s, a);
 }
 
-// the kernel family launch_one picks for a problem: 0 tile kernel, 5 ping-pong (whole tiles) or plain persistent
+// the size policy by tile count alone (a forced variant passes through): 0 a tile kernel, 5 ping-pong (whole tiles) or plain
+// persistent.  Asked by gemm_route only, which makes a kernel family of it.
 int size_policy(int M, int N) {
   int v = variant();
   if (v < 0) {  // auto: the persistent 256x256 kernel once its tiles cover most of the CUs, else the
@@ -1352,52 +1321,106 @@ int size_policy(int M, int N) {
   return v;
 }
 
-template <int PREC, int EPI>
-hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
-  int v = size_policy(a.M, a.N);
-#ifdef MCM_ARMS
-  if constexpr (epi_erf(EPI)) {  // the erf epilogue lives in the shipped kernels only: an arm would apply QuickGELU (or nothing)
-    if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk || v == 9) return hipErrorInvalidValue;  // (9: the arms' ping-pong text)
-  } else {  // A/B builds: the LayerNorm fold / tail forms and the forced arm variants (gemm_arms.hpp)
-    hipError_t e;
-    if (arms::route<PREC, EPI>(v, a, s, &e)) return e;
-  }
-#else
-  if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk) return hipErrorInvalidValue;  // A/B arms: not in the shipped library
+// ---- routing: the ONE answer to "which kernel does this problem get, and is it cut" ------------------------------------
+// launch_one switches on `family`; launch_gemm cuts the problem at `cut`; gemm_fold_kind, gemm_ln_tail_ok and
+// gemm_patch_takes_pixels read `policy`.  Nothing else decides.
+enum GemmFamily : int {
+  FAM_TILE,     // gemm_tile_kernel, one workgroup per 128x128 tile
+  FAM_TILE64,   // gemm_tile64_kernel, one workgroup per 64x128 tile
+  FAM_P256,     // gemm_p256_kernel, persistent 256x256 (edge tiles, the patch epilogue)
+  FAM_P256_PX,  // ... its pixel-gathering form (GemmArgs::px)
+  FAM_PP,       // gemm_pp_kernel, ping-pong 256x256 (whole tiles only)
+  FAM_P256_CS,  // gemm_p256_kernel with counted stores (harness variant 4)
+};
+struct GemmRoute {
+  int policy;         // size_policy(M, N): what the arms' routing (arms::route) and the gemm_* predicates see
+  GemmFamily family;  // the shipped kernel launch_one launches
+  int cut;            // sliver round: rows [0, cut) and [cut, M) are launched as two problems; 0 = not cut
+};
+GemmRoute gemm_route(int epi, int M, int N, bool px, int hm) {
+  GemmRoute r{size_policy(M, N), FAM_P256, 0};
+  const int G = persistent_grid();
+  const bool whole = M % p256::BM == 0 && N % p256::BN == 0;
+  int v = r.policy;
+#ifdef MCM_HARNESS
+  if (v == 9) v = 5;  // the arms' ping-pong text took its whole-tile problems in arms::route: what is left goes as 5 does
 #endif
-  if constexpr (EPI == EPI_PATCH) {
-    if (a.px) return launch_p256<PREC, EPI, false, true>(a, s);  // the pixel-gathering form of the persistent kernel
-  }
-  if (v == 0 || v == 11) {
+  if (epi == EPI_PATCH && px) {
+    r.family = FAM_P256_PX;  // the pixel-gathering form of the persistent kernel
+  } else if (v == 0 || v == 11) {
     // 64x128 tiles when the 128x128 kernel would get fewer than two workgroups per CU (batch <= 32 at B/16, the text
     // tower's short prompts banks, B/32): twice the workgroups, the same bits (round 3: batch 8 +7.5 %, batch 16 +4.5 %)
-    const bool few = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) < 2L * persistent_grid();
-    if (v == 11 || (variant() < 0 && few && !MCM_HM(a.hm))) return launch_tile64<PREC, EPI>(a, s);
-    return launch_tile<PREC, EPI>(a, s);
+    const bool few = (long)((M + 127) / 128) * ((N + 127) / 128) < 2L * G;
+    r.family = v == 11 || (variant() < 0 && few && !MCM_HM(hm)) ? FAM_TILE64 : FAM_TILE;
+  } else if (v == 4) {
+    r.family = FAM_P256_CS;
+  } else if (v == 5 && epi != EPI_PATCH && whole) {  // the patch epilogue remaps rows: stays with the plain kernel
+    r.family = FAM_PP;
   }
-#ifdef MCM_HARNESS
-  if (v == 4) return launch_p256<PREC, EPI, true>(a, s);
+#ifndef MCM_NO_SLIVER_SPLIT
+  // Sliver round.  The persistent kernel walks T = row tiles x N tiles on G workgroups; when T is a little more than
+  // a whole number of rounds, the last round keeps a few CUs busy for a full tile time while the rest of the chip
+  // idles — ViT-B/32 at batch 512: 100 row tiles x 3 = 300 tiles on 256 workgroups, 1 round + 44 tiles, paid as 2.
+  // Such a problem is cut at a row-tile boundary: the rows that fill whole rounds on every XCD (row tiles are dealt to
+  // the XCDs modulo 8, 1/8 of the workgroups each) go to the ping-pong kernel, the row tiles left over to a tile
+  // kernel, whose many small workgroups spread over the whole chip.  The kernels are bit-identical
+  // (tests/test_gpu_kernels.py::test_linear_sliver_split_bitwise), so the result does not depend on the cut.
+  if (epi != EPI_PATCH && variant() < 0 && G >= 8 && whole && r.policy == 5) {
+    const long nbn = N / p256::BN, rt = M / p256::BM, T = rt * nbn, R = T / G, left = T - R * G;
+    const long rt1 = 8 * ((R * (G / 8)) / nbn);  // row tiles of R whole rounds on each XCD
+    // ... worth it only when the rows left over make enough 128x128 workgroups to occupy the chip: a handful of
+    // them, one per CU with nobody to overlap with, take as long over a deep K as the round they replace (measured
+    // at ViT-L/14, where one row tile is left: 5 918 vs 5 921 img/s; ViT-B/32, 20 row tiles: +2.9 %)
+    const long rest_wgs = (rt - rt1) * 2 * (N / 128);
+    // (a last round up to a quarter full; up to half full measured equal or slower at batches 64 ... 512:
+    // profiles/r03_x_kernel_choice_small_batches.txt)
+    // ... and only when the left-over rows are a problem the size policy hands to the tile kernel (with a wide N the floor
+    // in rt1 can leave up to 8 nbn - 1 tiles, more than half a round: those would go back to a persistent kernel as a
+    // second ragged round — ADVICE r3)
+    if (R >= 1 && left > 0 && left * 4 <= G && rt1 >= 1 && rt1 < rt && rest_wgs * 2 >= G &&
+        size_policy((int)(rt1 * p256::BM), N) == 5 && size_policy((int)((rt - rt1) * p256::BM), N) == 0)
+      r.cut = (int)(rt1 * p256::BM);
+  }
 #endif
-  if (v == 5) {
-    if constexpr (EPI != EPI_PATCH) {  // the patch epilogue remaps rows: stays with the plain kernel
-      if (a.M % p256::BM == 0 && a.N % p256::BN == 0) return launch_pp<PREC, EPI>(a, s);
-    }
-  }
-  return launch_p256<PREC, EPI, false>(a, s);
+  return r;
 }
 
-// the split-output epilogues (EPI_*_X2; fp16 only): the shipped kernels under the shipped size policy, never an A/B arm
 template <int PREC, int EPI>
-hipError_t launch_one_x2(const GemmArgs& a, hipStream_t s) {
-  if constexpr (PREC != MCM_PREC_F16) {
+hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
+  if constexpr (epi_x2(EPI) && PREC != MCM_PREC_F16) {  // the split-output epilogues: fp16 only
     return hipErrorInvalidValue;
   } else {
-    const int v = size_policy(a.M, a.N);
-    if (v == 0 || v == 11) {
-      const bool few = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) < 2L * persistent_grid();
-      return few ? launch_tile64<PREC, EPI>(a, s) : launch_tile<PREC, EPI>(a, s);
+    const GemmRoute r = gemm_route(EPI, a.M, a.N, a.px != nullptr, a.hm);
+    // (... and the shipped kernels only, never an A/B arm: launch_gemm has refused a forced variant, hm and px with them)
+    if constexpr (!epi_x2(EPI)) {
+#ifdef MCM_ARMS
+      int v = r.policy;
+      if constexpr (epi_erf(EPI)) {  // the erf epilogue lives in the shipped kernels only: an arm would apply QuickGELU (or nothing)
+        if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk || v == 9) return hipErrorInvalidValue;  // (9: the arms' ping-pong text)
+      } else {  // A/B builds: the LayerNorm fold / tail forms and the forced arm variants (gemm_arms.hpp)
+        hipError_t e;
+        if (arms::route<PREC, EPI>(v, a, s, &e)) return e;
+      }
+#else
+      if (a.fold_z || a.fold_rs || a.ln_y || a.lnc || a.wblk) return hipErrorInvalidValue;  // A/B arms: not in the shipped library
+#endif
     }
-    if (a.M % p256::BM == 0 && a.N % p256::BN == 0) return launch_pp<PREC, EPI>(a, s);
+    switch (r.family) {
+      case FAM_TILE: return launch_tile<PREC, EPI>(a, s);
+      case FAM_TILE64: return launch_tile64<PREC, EPI>(a, s);
+      case FAM_PP:
+        if constexpr (EPI != EPI_PATCH) return launch_pp<PREC, EPI>(a, s);
+        break;
+      case FAM_P256_PX:
+        if constexpr (EPI == EPI_PATCH) return launch_p256<PREC, EPI, false, true>(a, s);
+        break;
+      case FAM_P256_CS:
+#ifdef MCM_HARNESS
+        if constexpr (!epi_x2(EPI)) return launch_p256<PREC, EPI, true>(a, s);
+#endif
+        break;
+      case FAM_P256: break;
+    }
     return launch_p256<PREC, EPI, false>(a, s);
   }
 }
@@ -1405,9 +1428,9 @@ hipError_t launch_one_x2(const GemmArgs& a, hipStream_t s) {
 template <int PREC>
 hipError_t launch_prec(int epi, const GemmArgs& a, hipStream_t s) {
   switch (epi) {
-    case EPI_STORE_X2: return launch_one_x2<PREC, EPI_STORE_X2>(a, s);
-    case EPI_GELU_X2: return launch_one_x2<PREC, EPI_GELU_X2>(a, s);
-    case EPI_GELU_ERF_X2: return launch_one_x2<PREC, EPI_GELU_ERF_X2>(a, s);
+    case EPI_STORE_X2: return launch_one<PREC, EPI_STORE_X2>(a, s);
+    case EPI_GELU_X2: return launch_one<PREC, EPI_GELU_X2>(a, s);
+    case EPI_GELU_ERF_X2: return launch_one<PREC, EPI_GELU_ERF_X2>(a, s);
     case EPI_STORE: return launch_one<PREC, EPI_STORE>(a, s);
     case EPI_GELU: return launch_one<PREC, EPI_GELU>(a, s);
     case EPI_GELU_ERF: return launch_one<PREC, EPI_GELU_ERF>(a, s);
@@ -1429,8 +1452,6 @@ void gemm_set_group_n(int gn) { g_group_n = gn > 0 ? gn : 0; }
 constexpr int g_group_n = 0, g_dbg = 0;
 #endif
 
-// LayerNorm in the tail: whether launch_gemm takes a residual GEMM of this size with GemmArgs::ln_y set (the ping-pong
-// kernel, whole tiles, rows of at most 1024 columns); the host then does not launch the LayerNorm that follows
 #ifdef MCM_HARNESS
 void gemm_set_persistent_grid(int n) { g_grid_override = n; }
 hipError_t launch_lnc_cleanup(int prec, const float* x, const float* g, const float* b, void* y, const float2* part, int M, int D,
@@ -1452,12 +1473,14 @@ hipError_t launch_gemm_row64_ln(int prec, const GemmArgs& a, hipStream_t s, int 
 }
 #endif
 int gemm_persistent_grid() { return persistent_grid(); }  // workgroups of the persistent kernels (one per CU, multiple of 8)
+// LayerNorm in the tail: whether launch_gemm takes a residual GEMM of this size with GemmArgs::ln_y set (the ping-pong
+// kernel, whole tiles, rows of at most 1024 columns); the host then does not launch the LayerNorm that follows
 bool gemm_ln_tail_ok(int prec, int M, int N) {
 #if !defined(MCM_HARNESS) && !defined(MCM_LN_TAIL)
   return false;  // the arm is not in this build
 #endif
   if (prec == MCM_PREC_F32 || M <= 0 || M % p256::BM || (N != 768 && N != 1024)) return false;
-  return size_policy(M, N) == 5 && persistent_grid() >= 8;
+  return gemm_route(EPI_RESID, M, N, false, 0).policy == 5 && persistent_grid() >= 8;
 }
 
 // The patch GEMM can gather its A operand from the NCHW fp32 pixels (GemmArgs::px) when the problem is one the persistent
@@ -1466,15 +1489,13 @@ bool gemm_patch_takes_pixels(int prec, int M, int N, int kpad, int patch, int im
   const int es = prec_esize(prec), ks = ROWB / es, ec = 16 / es;
   if (patch <= 0 || image % patch || patch % ec || ks % patch || kpad != 3 * patch * patch) return false;
   if ((size_t)M / ((size_t)(image / patch) * (image / patch)) * 3 * image * image * 4 >= (1ull << 32)) return false;  // 32-bit lane offsets
-  return size_policy(M, N) != 0 && persistent_grid() >= 8;
+  return gemm_route(EPI_PATCH, M, N, true, 0).policy != 0 && persistent_grid() >= 8;
 }
 
 int gemm_fold_kind(int epi, int M, int N) {
   if (epi == EPI_PATCH || epi_erf(epi) || M <= 0 || N <= 0) return 0;  // (the fold's consumer epilogue is QuickGELU's)
-  const int v = size_policy(M, N);
-  if (v == 5 && M % p256::BM == 0 && N % p256::BN == 0) return 1;
-  if (v == 0) return 2;
-  return 0;
+  const int v = gemm_route(epi, M, N, false, 0).policy;
+  return v == 5 && M % p256::BM == 0 && N % p256::BN == 0 ? 1 : v == 0 ? 2 : 0;
 }
 
 static hipError_t launch_gemm_one(int prec, int epi, const GemmArgs& a, hipStream_t s) {
@@ -1516,45 +1537,20 @@ hipError_t launch_gemm(int prec, int epi, const GemmArgs& a_in, hipStream_t s) {
 #ifndef MCM_HARNESS
   if (a.hm) return hipErrorInvalidValue;  // the head-major store path exists in the harness library only
 #endif
-#ifndef MCM_NO_SLIVER_SPLIT
-  // Sliver round.  The persistent kernel walks T = row tiles x N tiles on G workgroups; when T is a little more than
-  // a whole number of rounds, the last round keeps a few CUs busy for a full tile time while the rest of the chip
-  // idles — ViT-B/32 at batch 512: 100 row tiles x 3 = 300 tiles on 256 workgroups, 1 round + 44 tiles, paid as 2.
-  // Such a problem is cut at a row-tile boundary: the rows that fill whole rounds on every XCD (row tiles are dealt to
-  // the XCDs modulo 8, 1/8 of the workgroups each) go to the ping-pong kernel, the row tiles left over to the 128x128
-  // tile kernel, whose many small workgroups spread over the whole chip.  The kernels are bit-identical
-  // (tests/test_gpu_kernels.py::test_linear_sliver_split_bitwise), so the result does not depend on the cut.
-  {
-    const int G = persistent_grid();
-    const bool fold = a.fold_z != nullptr || a.fold_rs != nullptr;
-    if (epi != EPI_PATCH && !fold && !a.ln_y && variant() < 0 && G >= 8 && a.M % p256::BM == 0 && a.N % p256::BN == 0 &&
-        size_policy(a.M, a.N) == 5) {
-      const long nbn = a.N / p256::BN, rt = a.M / p256::BM, T = rt * nbn, R = T / G, left = T - R * G;
-      const long rt1 = 8 * ((R * (G / 8)) / nbn);  // row tiles of R whole rounds on each XCD
-      // ... worth it only when the rows left over make enough 128x128 workgroups to occupy the chip: a handful of
-      // them, one per CU with nobody to overlap with, take as long over a deep K as the round they replace (measured
-      // at ViT-L/14, where one row tile is left: 5 918 vs 5 921 img/s; ViT-B/32, 20 row tiles: +2.9 %)
-      const long rest_wgs = (rt - rt1) * 2 * (a.N / 128);
-      // (a last round up to a quarter full; up to half full measured equal or slower at batches 64 ... 512:
-      // profiles/r03_x_kernel_choice_small_batches.txt)
-      // ... and only when the left-over rows are a problem the size policy hands to the tile kernel (with a wide N the floor
-      // in rt1 can leave up to 8 nbn - 1 tiles, more than half a round: those would go back to a persistent kernel as a
-      // second ragged round — ADVICE r3)
-      if (R >= 1 && left > 0 && left * 4 <= G && rt1 >= 1 && rt1 < rt && rest_wgs * 2 >= G &&
-          size_policy((int)(rt1 * p256::BM), a.N) == 5 && size_policy((int)((rt - rt1) * p256::BM), a.N) == 0) {
-        GemmArgs m = a, r = a;
-        const size_t row0 = (size_t)rt1 * p256::BM;
-        m.M = (int)row0;
-        r.M = a.M - (int)row0;
-        r.x = (const char*)a.x + row0 * a.ldx * es;
-        if (a.out) r.out = (char*)a.out + (a.hm ? row0 * 64 : row0 * a.ldo) * es;
-        if (a.resid) r.resid = a.resid + row0 * a.ldo;
-        hipError_t e = launch_gemm_one(prec, epi, m, s);
-        return e != hipSuccess ? e : launch_gemm_one(prec, epi, r, s);
-      }
-    }
+  // sliver round (gemm_route): the rows that fill whole rounds of the ping-pong kernel, then the rest on a tile kernel.  The
+  // LayerNorm arms take their problems whole.
+  const int cut = gemm_route(epi, a.M, a.N, a.px != nullptr, a.hm).cut;
+  if (cut && !a.fold_z && !a.fold_rs && !a.ln_y) {
+    GemmArgs m = a, r = a;
+    const size_t row0 = (size_t)cut;
+    m.M = cut;
+    r.M = a.M - cut;
+    r.x = (const char*)a.x + row0 * a.ldx * es;
+    if (a.out) r.out = (char*)a.out + (a.hm ? row0 * 64 : row0 * a.ldo) * es;
+    if (a.resid) r.resid = a.resid + row0 * a.ldo;
+    hipError_t e = launch_gemm_one(prec, epi, m, s);
+    return e != hipSuccess ? e : launch_gemm_one(prec, epi, r, s);
   }
-#endif
   return launch_gemm_one(prec, epi, a, s);
 }
 

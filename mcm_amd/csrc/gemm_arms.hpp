@@ -1188,28 +1188,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmArgs a) {
 // ---- launchers of the arms ----------------------------------------------------------------------------------------
 template <int PREC, int EPI>
 hipError_t launch_tile_fold(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)arms::gemm_tile_kernel<PREC, EPI, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, tile::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
   const int nbn = (a.N + tile::BN - 1) / tile::BN, nbm = (a.M + tile::BM - 1) / tile::BM;
-  hipLaunchKernelGGL((arms::gemm_tile_kernel<PREC, EPI, true>), dim3(nbn * nbm), dim3(256), tile::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<arms::gemm_tile_kernel<PREC, EPI, true>, tile::LDS_BYTES>(dim3(nbn * nbm), dim3(256), tile::LDS_BYTES, s, a);
 }
 template <int PREC, int EPI, bool FOLD = false, bool LNT = false, bool LNC = false>
 hipError_t launch_pp(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)arms::gemm_pp_kernel<PREC, EPI, FOLD, LNT, LNC>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, p256::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL((arms::gemm_pp_kernel<PREC, EPI, FOLD, LNT, LNC>), dim3(persistent_grid()), dim3(512), p256::LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_lds<arms::gemm_pp_kernel<PREC, EPI, FOLD, LNT, LNC>, p256::LDS_BYTES>(dim3(persistent_grid()), dim3(512),
+                                                                                      p256::LDS_BYTES, s, a);
 }
 // LNC defer form: one 4-wave workgroup per (XCD, row panel, half).  Reads the half's mask (bit = 64-column slot whose LayerNorm
 // was written from registers), zeroes it, and — almost always — exits.  Otherwise: (mean, rstd) of the 128 rows from the slot
@@ -1494,17 +1479,9 @@ __global__ void row64_block_w_kernel(const uint4* __restrict__ w, uint4* __restr
 }
 template <int PREC, int FW, int NST>
 hipError_t launch_row64_ln_f(const GemmArgs& a, hipStream_t s) {
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_row64_ln_kernel<PREC, FW, NST>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       row64::lds_bytes<FW, NST>());
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
   const int ntiles = a.M / row64::BM, grid = ntiles < persistent_grid() ? ntiles : persistent_grid();
   constexpr int lds = row64::lds_bytes<FW, NST>();
-  hipLaunchKernelGGL((gemm_row64_ln_kernel<PREC, FW, NST>), dim3(grid), dim3(512), lds, s, a);
-  return hipGetLastError();
+  return launch_lds<gemm_row64_ln_kernel<PREC, FW, NST>, lds>(dim3(grid), dim3(512), lds, s, a);
 }
 // stages: 2 or 3 W stages per wave (3: N = 768 only — 160 KiB of LDS; other widths run 2)
 template <int PREC>

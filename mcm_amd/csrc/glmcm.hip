@@ -139,9 +139,6 @@ hipError_t launch_local_score(const float* rows, int B, int R, const float* bank
                               float* scores, float* patch, hipStream_t s) {
   if (B < 1 || R < 1 || K < 1 || P < 4 || P % 4 || (int64_t)B * R > INT_MAX || !(T > 0.f) || !isfinite(T))
     return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  hipError_t e = bank_sim::lds_limit_once(attr_set, (const void*)glm_rows_kernel, glm::LDS_BYTES);
-  if (e != hipSuccess) return e;
   GlmArgs a;
   a.rows = rows;
   a.bank = bank;
@@ -151,8 +148,8 @@ hipError_t launch_local_score(const float* rows, int B, int R, const float* bank
   a.M = B * R;
   a.P = P;
   a.K = K;
-  hipLaunchKernelGGL(glm_rows_kernel, dim3(bank_sim::query_tiles(a.M)), dim3(glm::THREADS), glm::LDS_BYTES, s, a);
-  e = hipGetLastError();
+  const hipError_t e =
+      launch_lds<glm_rows_kernel, glm::LDS_BYTES>(dim3(bank_sim::query_tiles(a.M)), dim3(glm::THREADS), glm::LDS_BYTES, s, a);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(glm_image_kernel, dim3((unsigned)B), dim3(glm::IMG_THREADS), 0, s, (const float*)work, R, scores);
   return hipGetLastError();

@@ -179,10 +179,7 @@ hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, i
                       float* scores, float* topv, hipStream_t s) {
   if (B < 1 || N < 1 || P < 4 || P % 4 || k < 1 || k > MCM_KNN_MAX_K || S < 1 || S > MCM_KNN_MAX_SPLITS)
     return hipErrorInvalidValue;
-  static PerDeviceFlag partial_set, merge_set;
-  hipError_t e = bank_sim::lds_limit_once(partial_set, (const void*)knn_partial_kernel, knn::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  e = bank_sim::lds_limit_once(merge_set, (const void*)knn_merge_kernel, knn::MERGE_LDS_MAX);
+  hipError_t e = lds_limit<knn_merge_kernel, knn::MERGE_LDS_MAX>();  // both limits stand before the first launch
   if (e != hipSuccess) return e;
   KnnArgs a;
   a.feats = feats;
@@ -194,13 +191,11 @@ hipError_t launch_knn(const float* feats, int B, const float* bank, int64_t N, i
   a.P = P;
   a.k = k;
   a.S = S;
-  hipLaunchKernelGGL(knn_partial_kernel, dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(knn::THREADS), knn::LDS_BYTES,
-                     s, a);
-  e = hipGetLastError();
+  e = launch_lds<knn_partial_kernel, knn::LDS_BYTES>(dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(knn::THREADS),
+                                                     knn::LDS_BYTES, s, a);
   if (e != hipSuccess) return e;
   int npow2 = 1;
   while (npow2 < S * k) npow2 <<= 1;
-  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)B), dim3(knn::THREADS), npow2 * sizeof(float), s, work, B, k, S,
-                     npow2, scores, topv);
-  return hipGetLastError();
+  return launch_lds<knn_merge_kernel, knn::MERGE_LDS_MAX>(dim3((unsigned)B), dim3(knn::THREADS), npow2 * (int)sizeof(float), s,
+                                                          work, B, k, S, npow2, scores, topv);
 }

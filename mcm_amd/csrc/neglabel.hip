@@ -131,9 +131,6 @@ hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, 
   if (B < 1 || K < 1 || G < 1 || G > MCM_NEG_MAX_GROUPS || gs < 1 || P < 4 || P % 4 || S < 1 || S > MCM_KNN_MAX_SPLITS ||
       !(T > 0.f) || !isfinite(T) || (int64_t)K + (int64_t)G * gs > INT_MAX)
     return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  hipError_t e = bank_sim::lds_limit_once(attr_set, (const void*)neg_partial_kernel, neg::LDS_BYTES);
-  if (e != hipSuccess) return e;
   const int N = K + G * gs;
   NegArgs a;
   a.feats = feats;
@@ -147,9 +144,8 @@ hipError_t launch_neglabel(const float* feats, int B, const float* bank, int K, 
   a.K = K;
   a.G = G;
   a.gs = gs;
-  hipLaunchKernelGGL(neg_partial_kernel, dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(neg::THREADS), neg::LDS_BYTES,
-                     s, a);
-  e = hipGetLastError();
+  const hipError_t e = launch_lds<neg_partial_kernel, neg::LDS_BYTES>(dim3(bank_sim::query_tiles(B), (unsigned)S),
+                                                                     dim3(neg::THREADS), neg::LDS_BYTES, s, a);
   if (e != hipSuccess) return e;
   NegCombineArgs c;
   c.work = (const float2*)work;

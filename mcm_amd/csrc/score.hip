@@ -373,17 +373,8 @@ hipError_t launch_score(const float* img, int B, const float* text, int K, int P
   if (B <= 0 || K <= 0 || P % 4 || kind < 0 || kind > MCM_SCORE_VAR || !(T > 0.f))
     return hipErrorInvalidValue;
   const int lds = (P + K) * (int)sizeof(float);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)score_kernel<false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL(score_kernel<false>, dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores,
-                     0, (int*)nullptr, (float*)nullptr);
-  return hipGetLastError();
+  return launch_lds<score_kernel<false>, 150 * 1024>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, 0,
+                                                     (int*)nullptr, (float*)nullptr);
 }
 
 bool score_shape_ok(int K, int P) { return K > 0 && P > 0 && P % 4 == 0 && (int64_t)(P + (int64_t)K) * 4 <= 150 * 1024; }
@@ -394,14 +385,6 @@ hipError_t launch_score_topk(const float* img, int B, const float* text, int K, 
       topk > MCM_TOPK_MAX || !scores || !idx)
     return hipErrorInvalidValue;
   const int lds = (P + K) * (int)sizeof(float);
-  static PerDeviceFlag attr_set;
-  if (!attr_set.get()) {
-    hipError_t e = hipFuncSetAttribute((const void*)score_kernel<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.set();
-  }
-  hipLaunchKernelGGL(score_kernel<true>, dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores,
-                     topk, idx, prob);
-  return hipGetLastError();
+  return launch_lds<score_kernel<true>, 150 * 1024>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, topk, idx,
+                                                    prob);
 }

@@ -143,9 +143,6 @@ hipError_t launch_vim(const float* feats, int B, const float* bank, int K, int R
   if (B < 1 || K < 1 || R < 1 || P < 4 || P % 4 || S < 1 || S > MCM_KNN_MAX_SPLITS || !(T > 0.f) || !isfinite(T) ||
       !isfinite(alpha) || (int64_t)K + (int64_t)R > INT_MAX)
     return hipErrorInvalidValue;
-  static PerDeviceFlag attr_set;
-  hipError_t e = bank_sim::lds_limit_once(attr_set, (const void*)vim_partial_kernel, vim::LDS_BYTES);
-  if (e != hipSuccess) return e;
   const int N = K + R;
   VimArgs a;
   a.feats = feats;
@@ -158,9 +155,8 @@ hipError_t launch_vim(const float* feats, int B, const float* bank, int K, int R
   a.B = B;
   a.P = P;
   a.K = K;
-  hipLaunchKernelGGL(vim_partial_kernel, dim3(bank_sim::query_tiles(B), (unsigned)S), dim3(vim::THREADS), vim::LDS_BYTES,
-                     s, a);
-  e = hipGetLastError();
+  const hipError_t e = launch_lds<vim_partial_kernel, vim::LDS_BYTES>(dim3(bank_sim::query_tiles(B), (unsigned)S),
+                                                                     dim3(vim::THREADS), vim::LDS_BYTES, s, a);
   if (e != hipSuccess) return e;
   VimCombineArgs c;
   c.work = (const VimSlot*)work;

@@ -125,7 +125,8 @@ def test_gemm_edge_shapes_within_budget(gemm_net, prec, epi):
 FULL = [
     ("B16-b512", 512 * 197, [(2304, 768, 0), (3072, 768, 1), (768, 3072, 2), (768, 768, 2)], ()),
     ("L14-b256", 256 * 257, [(3072, 1024, 0), (4096, 1024, 1), (1024, 4096, 2), (1024, 1024, 2)], ()),
-    # the sliver split of launch_gemm cuts ViT-B/32 at batch 512 at row 80 * 256 (ping-pong above, tile kernel below)
+    # the sliver split of launch_gemm cuts the N = 768 problems of ViT-B/32 at batch 512 (out-proj, fc2) at row 80 * 256: ping-pong
+    # above, the 64x128 tile kernel below; QKV and fc1 go to the ping-pong kernel whole (tests/test_launch_routes_cpu.py)
     ("B32-b512", 512 * 50, [(2304, 768, 0), (3072, 768, 1), (768, 3072, 2), (768, 768, 2)], (20479, 20480, 20481)),
     # the text tower at K = 1000 prompts: 301 row tiles, the last one ragged -> the ragged persistent kernel
     ("text-K1000", 1000 * 77, [(1536, 512, 0), (512, 512, 2), (2048, 512, 1), (512, 2048, 2)], ()),
