@@ -2,6 +2,8 @@
 struct's fields and a constant's value.  Standard library only.
 
     PROTOTYPES / HARNESS_PROTOTYPES   name -> (restype, argtypes): the product entries / those under #ifdef MCM_HARNESS
+    EXTENSION_PROTOTYPES              the same for the product entries that the extension headers next to mcm.h declare
+                                      (include/mcm_score_stream.h); declare() binds them where they are named
     DEFINES                           every integer `#define MCM_*` -> int
     struct_fields(name)               the ctypes `_fields_` of a struct of the header, array members included
     declare(lib, names, harness)      sets restype and argtypes on a ctypes.CDLL
@@ -20,6 +22,7 @@ import re
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mcm.h")
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
             **{f"{u}int{n}_t": getattr(ctypes, f"c_{u}int{n}") for u in ("", "u") for n in (8, 16, 32, 64)}}
+EXTENSION_HEADERS = ("mcm_score_stream.h",)   # read by the rules of mcm.h; each includes it and adds entries, nothing else
 Header = collections.namedtuple("Header", "prototypes harness_prototypes defines structs")
 
 
@@ -74,15 +77,21 @@ def parse(text: str) -> Header:
     return Header(_prototypes(text), _prototypes(harness[1]) if harness else {}, defines, structs)
 
 
-def _read_header() -> Header:
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} not found: the Python binding of libmcm_hip.so is read from it "
+def _read_header(path: str = HEADER_PATH) -> Header:
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the Python binding of libmcm_hip.so is read from it "
                            "(mcm_amd runs from its source tree, next to include/)")
-    with open(HEADER_PATH) as f:
+    with open(path) as f:
         return parse(f.read())
 
 
 PROTOTYPES, HARNESS_PROTOTYPES, DEFINES, _STRUCTS = _read_header()
+EXTENSION_PROTOTYPES = {}
+for _name in EXTENSION_HEADERS:
+    _ext = _read_header(os.path.join(os.path.dirname(HEADER_PATH), _name))
+    if _ext.harness_prototypes or _ext.defines or _ext.structs or set(_ext.prototypes) & set(PROTOTYPES):
+        raise ValueError(f"include/{_name}: an extension header declares new product entries and nothing else")
+    EXTENSION_PROTOTYPES.update(_ext.prototypes)
 
 
 def struct_fields(name: str) -> list:
@@ -92,7 +101,7 @@ def struct_fields(name: str) -> list:
 def declare(lib, names=None, harness: bool = False):
     """Set restype and argtypes of `names` on `lib` (default: every product entry, and every harness entry with `harness`) and
     return it.  A symbol the library lacks is an error that names it; so is a name the header does not declare."""
-    table = {**PROTOTYPES, **HARNESS_PROTOTYPES}
+    table = {**PROTOTYPES, **HARNESS_PROTOTYPES, **EXTENSION_PROTOTYPES}
     if names is None:
         names = list(PROTOTYPES) + (list(HARNESS_PROTOTYPES) if harness else [])
     for name in names:

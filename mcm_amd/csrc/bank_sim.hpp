@@ -7,6 +7,7 @@
 // rows.  lse_fold takes columns of a tile row into a query's open pair (max, sum exp((s - max) / T)), the sum in fp64; the
 // open pairs of a workgroup's queries lie behind the tile (PAIR_BYTES, pair_sums, pair_maxima, pair_reset); lse_merge adds
 // the pairs that the splits of a bank left (neglabel.hip, vim.hip; glmcm.hip walks the whole bank in one workgroup).
+// score_stream.hip walks like the others and folds with softmax_moments_fold, which carries two more sums than lse_fold.
 #pragma once
 #include "common.hpp"
 
@@ -159,6 +160,41 @@ __device__ __forceinline__ double lse_merge(int s0, int s1, double inv_t, float&
     tot += v.x == M ? (double)v.y : (double)v.y * exp(((double)v.x - (double)M) * inv_t);
   }
   return tot;
+}
+
+// The fold of score_stream.hip: lse_fold with two more sums, for the scores that need more of a softmax than its
+// normaliser.  With x = (s - m) / T at the running maximum m the open state is Z = sum exp(x), W = sum x exp(x),
+// Q2 = sum exp(2 x), all fp64.  When the maximum rises from m to M, with d = (m - M) / T and a = exp(d):
+// Z <- a Z, W <- a (W + d Z), Q2 <- a^2 Q2 (m = -inf: nothing has been folded, the sums are 0 and stay 0).  exp(2 x) is
+// the square of the exp(x) that Z takes.  Every lane ends with the same m, Z, W, Q2.  A NaN is skipped by the maximum and
+// poisons the three sums.
+__device__ __forceinline__ void softmax_moments_fold(const float* row, int c, int ce, int lane, double inv_t, float& m,
+                                                     double& Z, double& W, double& Q2) {
+  float mx = -INFINITY;
+  for (int i = c + lane; i < ce; i += 64) mx = fmaxf(mx, row[i]);
+  const float M = fmaxf(m, wave_max(mx));
+  double pz = 0.0, pw = 0.0, pq = 0.0;
+  for (int i = c + lane; i < ce; i += 64) {
+    const double x = ((double)row[i] - (double)M) * inv_t;
+    const double e = exp(x);
+    pz += e;
+    pw = fma(x, e, pw);
+    pq = fma(e, e, pq);
+  }
+  pz = wave_sum(pz);
+  pw = wave_sum(pw);
+  pq = wave_sum(pq);
+  if (m != M && m != -INFINITY) {
+    const double d = ((double)m - (double)M) * inv_t;
+    const double a = exp(d);
+    W = a * fma(d, Z, W);
+    Z *= a;
+    Q2 *= a * a;
+  }
+  Z += pz;
+  W += pw;
+  Q2 += pq;
+  m = M;
 }
 
 inline unsigned query_tiles(int B) { return (unsigned)(((int64_t)B + Q - 1) / Q); }

@@ -493,6 +493,14 @@ bool score_shape_ok(int K, int P);
 hipError_t launch_score_topk(const float* img, int B, const float* text, int K, int P, float T, int kind,
                              int topk, float* scores, int* idx, float* prob, hipStream_t s);
 
+// score_stream.hip: the same five scores and top-k matches with the bank streamed through bank_sim.hpp's walk in S splits, for
+// any K <= INT_MAX: scores [B] the requested kind, parts [B, 5] (or nullptr) all five in MCM_SCORE_* order, idx / prob
+// [B, topk] (topk > 0; prob may be nullptr).  work holds score_stream_work_bytes(B, topk, S): one 32-byte slot and topk
+// 8-byte list entries per (split, query).
+int64_t score_stream_work_bytes(int B, int topk, int S);
+hipError_t launch_score_stream(const float* feats, int B, const float* bank, int K, int P, float T, int kind, int topk, int S,
+                               void* work, float* scores, float* parts, int* idx, float* prob, hipStream_t s);
+
 // metrics.hip: AUROC / AUPR / FPR@recall of two device score vectors; results land in the first
 // 4 doubles of `workspace` (>= measures_workspace_bytes(n_pos + n_neg)), *out_dev points at them
 size_t measures_workspace_bytes(long n);

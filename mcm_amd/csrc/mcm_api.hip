@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/mcm_score_stream.h"
 #include "bank_sim.hpp"
 #include "common.hpp"
 
@@ -946,6 +947,42 @@ int mcm_vim_score_features(mcm_handle* h, const float* feats_dev, int32_t B, con
   hipStream_t s = (hipStream_t)stream;
   Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * ((double)K + (double)R) * h->cfg.proj_dim);
   HIP_TRY(h, launch_vim(feats_dev, B, bank_dev, K, R, h->cfg.proj_dim, off_dev, T, alpha, S, work_dev, scores_dev, parts_dev, s));
+  return MCM_OK;
+}
+
+// ---- the streamed tail of the MCM family (include/mcm_score_stream.h) ----
+namespace {
+bool score_stream_ok(int64_t K, int32_t kind, int32_t topk) {
+  return K >= 1 && K <= INT32_MAX && kind >= 0 && kind <= MCM_SCORE_VAR && topk >= 0 && topk <= MCM_TOPK_MAX;
+}
+}  // namespace
+
+int mcm_score_stream_workspace_bytes(const mcm_handle* h, int32_t B, int64_t K, int32_t topk, int32_t splits,
+                                     int64_t* bytes_out) {
+  int S = 0;
+  if (!bytes_out || !bank_args_ok(h, score_stream_ok(K, MCM_SCORE_MCM, topk), B, K, splits, &S)) return MCM_EINVAL;
+  *bytes_out = score_stream_work_bytes(B, topk, S);
+  return MCM_OK;
+}
+
+int mcm_score_features_stream(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev, int64_t K,
+                              float T, int32_t kind, int32_t topk, int32_t splits, void* work_dev, int64_t work_bytes,
+                              float* scores_dev, float* parts_dev, int32_t* idx_dev, float* prob_dev, void* stream) {
+  if (!h) return MCM_EINVAL;
+  int S = 0;
+  if (!img_feat_dev || !text_feat_dev || !work_dev || !scores_dev ||
+      !bank_args_ok(h, score_stream_ok(K, kind, topk), B, K, splits, &S))
+    return fail(h, MCM_EINVAL, "bad argument");
+  if (topk > 0 && !idx_dev) return fail(h, MCM_EINVAL, "idx_dev is NULL with topk > 0");
+  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if ((uintptr_t)work_dev & 7) return fail(h, MCM_EINVAL, "work_dev must be 8-byte aligned");
+  if (int rc = bank_buffers(h, img_feat_dev, text_feat_dev, work_bytes, score_stream_work_bytes(B, topk, S),
+                            "work_bytes is below mcm_score_stream_workspace_bytes"))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(h, s, MCM_KC_SCORE, 2.0 * B * (double)K * h->cfg.proj_dim);
+  HIP_TRY(h, launch_score_stream(img_feat_dev, B, text_feat_dev, (int)K, h->cfg.proj_dim, T, kind, topk, S, work_dev,
+                                 scores_dev, parts_dev, idx_dev, prob_dev, s));
   return MCM_OK;
 }
 

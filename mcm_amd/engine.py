@@ -193,11 +193,17 @@ class NativeCLIP:
         if self.x2_default:
             return self.get_image_features_x2(pixel_values, normalize=normalize)
         px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0
         out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        for s, n in self._chunks(px.shape[0], self.max_batch):
-            self._check(self._lib.mcm_encode_image_ex(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)),
-                                                      out[s:s + n].data_ptr(), _stream_ptr()))
+        return self._encode_into(px, out, normalize, x2=False)
+
+    def _encode_into(self, px, out, normalize: bool, x2: bool):
+        """The image tower over `px` (as `_pixels` returns them) into out [b,P], in chunks of the arm's largest batch."""
+        import torch
+
+        fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
+        fn = self._lib.mcm_encode_image_x2 if x2 else self._lib.mcm_encode_image_ex
+        for s, n in self._chunks(px.shape[0], self._x2_batch() if x2 else self.max_batch):
+            self._check(fn(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)), out[s:s + n].data_ptr(), _stream_ptr()))
         return out
 
     def get_image_features_raw(self, pixel_values):
@@ -555,17 +561,27 @@ class NativeCLIP:
                                                  idx[s:s + n].data_ptr(), prob[s:s + n].data_ptr(), _stream_ptr()))
         return out, idx, prob
 
-    def score_features(self, image_features, text_features, T: float = 1.0, score: str = "MCM", topk: int = 0):
+    def score_features(self, image_features, text_features, T: float = 1.0, score: str = "MCM", topk: int = 0,
+                       tail: str = "lds", splits: int = 0, return_parts: bool = False):
         """features [b,P] + bank [K,P] → scores [b] fp32 on the device.  `topk` > 0 (at most 8): also which concepts
         matched — returns (scores, idx [b,topk] int32, prob [b,topk] fp32): the bank rows of the topk largest
         similarities (value descending, ties to the lower row, NaN never, -1 where nothing is left) and their
-        softmax(sim / T); the scores are the bits of the `topk=0` call (include/mcm.h mcm_score_features_topk)."""
+        softmax(sim / T); the scores are the bits of the `topk=0` call (include/mcm.h mcm_score_features_topk).
+        `tail`: "lds" = the tail that keeps an image's K similarities in LDS and refuses (P + K) * 4 > 150 KiB; "stream" = the
+        streamed tail (include/mcm_score_stream.h mcm_score_features_stream), any K; "auto" = "lds" wherever it takes the
+        shape, "stream" exactly where it refuses.  The default here is "lds": this call's refusal of a bank past that size is
+        part of its contract (tests/test_gpu_error_budget.py holds it); `score_images` / `score_images_x2`, which everything
+        in detection.py and refine.py goes through, default to "auto".  The streamed tail alone takes `splits` (0 = the library's choice, n = the
+        bank in exactly n ranges: results agree across it to rounding and are the same bits for a fixed value) and
+        `return_parts=True`, which appends parts [b,5], all five kinds in SCORE_KINDS order, to what is returned."""
         import torch
 
         f = image_features.to(device=self.device, dtype=torch.float32).contiguous()
         if f.dim() != 2 or f.shape[1] != self.geo.proj_dim:
             raise ValueError(f"image_features must be [b,{self.geo.proj_dim}], got {tuple(f.shape)}")
         t = self._bank(text_features)
+        if self._streams(tail, t.shape[0], splits, return_parts):
+            return self._score_stream(f, t, T, score, topk, splits, return_parts)
         if topk:
             out, idx, prob = self._topk_out(f.shape[0], topk)
             self._check(self._lib.mcm_score_features_topk(self._h, f.data_ptr(), f.shape[0], t.data_ptr(), t.shape[0],
@@ -578,19 +594,97 @@ class NativeCLIP:
                                                  out.data_ptr(), _stream_ptr()))
         return out
 
-    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
+    def score_kinds(self, image_features, text_features, T: float = 1.0, splits: int = 0):
+        """features [b,P] + bank [K,P] → [b,5] fp32: MCM, max-logit, energy, entropy and var (SCORE_KINDS order) from one walk
+        of the bank by the streamed tail, at any K."""
+        return self.score_features(image_features, text_features, T, "MCM", tail="stream", splits=splits, return_parts=True)[1]
+
+    # -- the streamed tail of the MCM family (include/mcm_score_stream.h; DESIGN.md 4.18) ---------------------------------
+    def _streams(self, tail, K, splits, return_parts) -> bool:
+        """Whether a call goes to the streamed tail.  "auto" sends it there exactly where the LDS tail refuses the shape
+        (csrc/score.hip score_shape_ok: (P + K) * 4 bytes of LDS above 150 KiB)."""
+        if tail not in ("auto", "lds", "stream"):
+            raise ValueError(f"tail must be 'auto', 'lds' or 'stream', got {tail!r}")
+        stream = tail == "stream" or (tail == "auto" and (self.geo.proj_dim + int(K)) * 4 > 150 * 1024)
+        if not stream and (splits or return_parts):
+            raise ValueError("splits and return_parts belong to the streamed tail: pass tail='stream'")
+        return stream
+
+    def _score_stream(self, f, t, T, score, topk, splits, return_parts, out=None):
+        """The streamed tail over features f [b,P] and bank t [K,P] (both as the kernels read them).  Returns scores, or
+        (scores, idx, prob) with topk > 0, with parts [b,5] appended where asked for.  The workspace is a buffer of this
+        object that grows on demand; queries go through in blocks of at most 4096 rows."""
+        import torch
+
+        if not getattr(self._lib, "_mcm_score_stream", False):  # the extension header's entries are bound where they are used
+            abi.declare(self._lib, names=list(abi.EXTENSION_PROTOTYPES))
+            self._lib._mcm_score_stream = True
+        B, K, T, kind, topk, splits = int(f.shape[0]), int(t.shape[0]), float(T), SCORE_KINDS[score], int(topk), int(splits)
+        if topk:
+            scores, idx, prob = self._topk_out(B, topk)
+        else:
+            scores = torch.empty(B, device=self.device, dtype=torch.float32) if out is None else out
+            idx = prob = None
+        parts = torch.empty((B, 5), device=self.device, dtype=torch.float32) if return_parts else None
+        self._bank_score("_score_stream_work", B, lambda n, need: self._check_score_stream(
+            self._lib.mcm_score_stream_workspace_bytes(self._h, n, K, topk, splits, need), n, K, T, topk, splits),
+            lambda s, n, work: self._check_score_stream(self._lib.mcm_score_features_stream(
+                self._h, f[s:s + n].data_ptr(), n, t.data_ptr(), K, T, kind, topk, splits, work.data_ptr(), work.numel() * 4,
+                scores[s:s + n].data_ptr(), parts[s:s + n].data_ptr() if return_parts else None,
+                idx[s:s + n].data_ptr() if topk else None, prob[s:s + n].data_ptr() if topk else None, _stream_ptr()),
+                n, K, T, topk, splits))
+        res = (scores, idx, prob) if topk else (scores,)
+        res = res + (parts,) if return_parts else res
+        return res if len(res) > 1 else res[0]
+
+    def _check_score_stream(self, rc, B, K, T, topk, splits):
+        if rc == -1:
+            import math
+
+            bad = [what for what, wrong in (
+                (f"B={B} (B >= 1)", B < 1), (f"K={K} (1 <= K <= 2^31 - 1)", not 1 <= K <= 2 ** 31 - 1),
+                (f"T={T} (positive and finite)", not (T > 0 and math.isfinite(T))),
+                (f"topk={topk} (0 <= topk <= {TOPK_MAX})", not 0 <= topk <= TOPK_MAX),
+                (f"splits={splits} (0 <= splits <= 32)", not 0 <= splits <= 32),
+                (f"proj_dim={self.geo.proj_dim} (proj_dim % 4 == 0)", self.geo.proj_dim % 4 != 0)) if wrong]
+            raise ValueError("score_features (streamed tail): refused (rc=-1): " + ("; ".join(bad) if bad else
+                             f"B={B}, K={K}, T={T}, topk={topk}, splits={splits}: " + self._lib.mcm_last_error(self._h).decode()))
+        self._check(rc)
+
+    def _score_images_stream(self, pixel_values, t, T, score, out, topk, x2, splits, return_parts):
+        """`score_images` / `score_images_x2` by the streamed tail: `get_image_features(normalize=True)` of the arm into a
+        buffer of this object that grows on demand, then `_score_stream` on it — the bits of
+        `score_features(get_image_features(pixel_values, normalize=True), ..., tail="stream")`."""
+        import torch
+
+        if x2:
+            self._x2_batch()
+        px = self._pixels(pixel_values)
+        b = px.shape[0]
+        feat = getattr(self, "_score_stream_feat", None)
+        if feat is None or feat.shape[0] < b:
+            feat = self._score_stream_feat = torch.empty((b, self.geo.proj_dim), device=self.device, dtype=torch.float32)
+        self._encode_into(px, feat[:b], True, x2)
+        return self._score_stream(feat[:b], t, T, score, topk, splits, return_parts, out=out)
+
+    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0,
+                     tail: str = "auto", splits: int = 0, return_parts: bool = False):
         """pixels [b,3,S,S] + pre-encoded bank [K,P] → scores [b] fp32 on device (one
         iteration of the reference loop, utils/detection_util.py:223-248).  `topk` > 0: (scores, idx, prob) as
-        `score_features` returns them (`out` is not used then)."""
+        `score_features` returns them (`out` is not used then).  `tail`, `splits`, `return_parts`: as `score_features`; past
+        the LDS tail's bank size the call is the image tower followed by the streamed tail."""
         import torch
 
         if self.x2_default:
-            return self.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk)
+            return self.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk, tail=tail, splits=splits,
+                                        return_parts=return_parts)
+        t = self._bank(text_features)
+        if self._streams(tail, t.shape[0], splits, return_parts):
+            return self._score_images_stream(pixel_values, t, T, score, out, topk, False, splits, return_parts)
         if topk:
             return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=False)
         px = self._pixels(pixel_values)
         fn = self._lib.mcm_score_u8 if px.dtype == torch.uint8 else self._lib.mcm_score
-        t = self._bank(text_features)
         if out is None:
             out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
         for s, n in self._chunks(px.shape[0], self.max_batch):
@@ -609,18 +703,22 @@ class NativeCLIP:
         """Non-zero when a persistent kernel gave up a bounded wait (include/mcm.h mcm_kernel_faults): 0 in every correct run."""
         return int(self._lib.mcm_kernel_faults(self._h))
 
-    def score_images_x2(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
+    def score_images_x2(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0,
+                        tail: str = "auto", splits: int = 0, return_parts: bool = False):
         """`score_images` through the split-activation arm: the same weights and workspace, every MFMA operand activation as a
         hi + lo pair of fp16 numbers — scores that agree with the exact-fp32 arm to fp32 round-off, at several times its
-        speed.  Any number of images (chunks of `x2_max_batch`).  `topk` > 0: (scores, idx, prob), as `score_images`."""
+        speed.  Any number of images (chunks of `x2_max_batch`).  `topk` > 0: (scores, idx, prob), as `score_images`;
+        `tail`, `splits`, `return_parts` too."""
         import torch
 
+        t = self._bank(text_features)
+        if self._streams(tail, t.shape[0], splits, return_parts):
+            return self._score_images_stream(pixel_values, t, T, score, out, topk, True, splits, return_parts)
         if topk:
             return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=True)
         nb = self._x2_batch()
         px = self._pixels(pixel_values)
         fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
-        t = self._bank(text_features)
         if out is None:
             out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
         for s, n in self._chunks(px.shape[0], nb):
@@ -632,14 +730,10 @@ class NativeCLIP:
         """`get_image_features` through the split-activation arm (raw projected features unless `normalize`)."""
         import torch
 
-        nb = self._x2_batch()
+        self._x2_batch()
         px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0
         out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        for s, n in self._chunks(px.shape[0], nb):
-            self._check(self._lib.mcm_encode_image_x2(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)),
-                                                      out[s:s + n].data_ptr(), _stream_ptr()))
-        return out
+        return self._encode_into(px, out, normalize, x2=True)
 
     def x2_scorer(self):
         """An object with this scorer's `score_images` signature that runs the split-activation arm (mcm_amd.refine.Rescorer)."""
@@ -771,8 +865,9 @@ class _X2Scorer:
         self.net, self.device, self.geo = net, net.device, net.geo
         self.max_batch = net.x2_max_batch
 
-    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0):
-        return self.net.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk)
+    def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0,
+                     tail: str = "auto"):
+        return self.net.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk, tail=tail)
 
 
 class GraphedScorer:
