@@ -241,6 +241,7 @@ int mcm_score(mcm_handle* h, const float* pixels_dev, int32_t B, const float* te
  * the workspace, B <= the arm's largest batch — otherwise MCM_EINVAL / MCM_ERANGE), x2 == 0 the handle's own arm through
  * the encode calls of mcm_score / mcm_score_u8.  Asynchronous on `stream`, no allocation, graph-capturable. */
 #define MCM_TOPK_MAX 8
+#define MCM_SCORE_LDS_MAX_BYTES 153600 /* 150 KiB: the LDS of the tail that keeps (proj_dim + K) floats per image */
 int mcm_score_features_topk(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev,
                             int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev,
                             int32_t* idx_dev /* [B,topk] */, float* prob_dev /* [B,topk] or NULL */, void* stream);

@@ -120,6 +120,13 @@ int fail(HandleCore* h, int code, const std::string& msg) {
       return fail(h, MCM_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
+// The two argument rules every scoring entry repeats: a temperature is positive and finite, a pixel_format is one of MCM_PIXELS_*
+bool bad_temperature(float T) { return !(T > 0.f) || !std::isfinite(T); }
+int check_pixel_format(HandleCore* h, int32_t pixel_format) {
+  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC) return fail(h, MCM_EINVAL, "unknown pixel_format");
+  return MCM_OK;
+}
+
 void add_param(HandleCore* h, const std::string& name, std::vector<int64_t> shape) {
   Param p;
   p.shape = shape;
@@ -790,8 +797,7 @@ int mcm_encode_image_raw(mcm_handle* h, const float* pixels_dev, int32_t B, floa
 
 int mcm_encode_image_ex(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B,
                         int32_t normalize, float* out_dev, void* stream) {
-  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC)
-    return fail(h, MCM_EINVAL, "unknown pixel_format");
+  if (int rc = check_pixel_format(h, pixel_format)) return rc;
   return encode_image_impl(h, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, out_dev, stream,
                            normalize != 0);
 }
@@ -802,8 +808,7 @@ int mcm_kernel_faults(const mcm_handle* h) { return h && h->fault_pin ? (int)*(v
 
 int mcm_encode_image_x2(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, int32_t normalize,
                         float* out_dev, void* stream) {
-  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC)
-    return fail(h, MCM_EINVAL, "unknown pixel_format");
+  if (int rc = check_pixel_format(h, pixel_format)) return rc;
   return encode_image_impl(h, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, out_dev, stream, normalize != 0, true);
 }
 
@@ -908,7 +913,7 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev, int32_t B
   if (!feats_dev || !bank_dev || !work_dev || !scores_dev ||
       !bank_args_ok(h, neglabel_ok(K, G, gs), B, (int64_t)K + (int64_t)G * gs, splits, &S))
     return fail(h, MCM_EINVAL, "bad argument");
-  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (bad_temperature(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
   if (int rc = bank_buffers(h, feats_dev, bank_dev, work_bytes, neglabel_work_bytes(B, G, S),
                             "work_bytes is below mcm_neglabel_workspace_bytes"))
     return rc;
@@ -938,7 +943,7 @@ int mcm_vim_score_features(mcm_handle* h, const float* feats_dev, int32_t B, con
   if (!feats_dev || !bank_dev || !work_dev || !scores_dev ||
       !bank_args_ok(h, vim_ok(K, R), B, (int64_t)K + (int64_t)R, splits, &S))
     return fail(h, MCM_EINVAL, "bad argument");
-  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (bad_temperature(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
   if (!std::isfinite(alpha)) return fail(h, MCM_EINVAL, "alpha must be finite");
   if (((uintptr_t)off_dev | (uintptr_t)work_dev) & 7) return fail(h, MCM_EINVAL, "off_dev / work_dev must be 8-byte aligned");
   if (int rc = bank_buffers(h, feats_dev, bank_dev, work_bytes, vim_work_bytes(B, S),
@@ -974,7 +979,7 @@ int mcm_score_features_stream(mcm_handle* h, const float* img_feat_dev, int32_t 
       !bank_args_ok(h, score_stream_ok(K, kind, topk), B, K, splits, &S))
     return fail(h, MCM_EINVAL, "bad argument");
   if (topk > 0 && !idx_dev) return fail(h, MCM_EINVAL, "idx_dev is NULL with topk > 0");
-  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (bad_temperature(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
   if ((uintptr_t)work_dev & 7) return fail(h, MCM_EINVAL, "work_dev must be 8-byte aligned");
   if (int rc = bank_buffers(h, img_feat_dev, text_feat_dev, work_bytes, score_stream_work_bytes(B, topk, S),
                             "work_bytes is below mcm_score_stream_workspace_bytes"))
@@ -1041,7 +1046,7 @@ int local_pass(mcm_handle* h, hipStream_t s, int32_t B, float* local_dev) {
 int encode_image_local_impl(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, float* global_dev,
                             float* local_dev, void* stream) {
   if (!h) return MCM_EINVAL;
-  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC) return fail(h, MCM_EINVAL, "unknown pixel_format");
+  if (int rc = check_pixel_format(h, pixel_format)) return rc;
   int rc = check_image_call(h, pixels_dev, global_dev, B, false);
   if (rc) return rc;
   if (!local_dev) return fail(h, MCM_EINVAL, "null pointer");
@@ -1064,7 +1069,7 @@ int mcm_local_score_features(mcm_handle* h, const float* local_dev, int32_t B, i
   if (!h) return MCM_EINVAL;
   if (!local_dev || !text_dev || !work_dev || !local_scores_dev || !local_args_ok(h, B, R, K))
     return fail(h, MCM_EINVAL, "bad argument");
-  if (!(T > 0.f) || !std::isfinite(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
+  if (bad_temperature(T)) return fail(h, MCM_EINVAL, "T must be positive and finite");
   if (((uintptr_t)local_dev | (uintptr_t)text_dev) & 15) return fail(h, MCM_EINVAL, "local_dev / text_dev must be 16-byte aligned");
   if (((uintptr_t)work_dev | (uintptr_t)local_scores_dev | (uintptr_t)patch_dev) & 3)
     return fail(h, MCM_EINVAL, "work_dev / local_scores_dev / patch_dev must be 4-byte aligned");
@@ -1085,7 +1090,7 @@ int mcm_score_glmcm(mcm_handle* h, const void* pixels_dev, int32_t pixel_format,
                     float* patch_dev, void* stream) {
   if (!h) return MCM_EINVAL;
   if (!text_dev || !scores_dev) return fail(h, MCM_EINVAL, "null pointer");
-  if (K < 1 || !(T > 0.f) || !std::isfinite(T) || !std::isfinite(lambda)) return fail(h, MCM_EINVAL, "bad K / T / lambda");
+  if (K < 1 || bad_temperature(T) || !std::isfinite(lambda)) return fail(h, MCM_EINVAL, "bad K / T / lambda");
   if ((uintptr_t)text_dev & 15) return fail(h, MCM_EINVAL, "text_dev must be 16-byte aligned");
   // the compacted local rows go where out_proj's rows were (h->x is dead again behind post_layernorm: B R P <= B ntok D
   // floats, check_local_call); the row values and the parts nobody asked for go to h->att, which is dead as well
@@ -1445,8 +1450,7 @@ int mcm_score_topk(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, 
                    const float* text_feat_dev, int32_t K, float T, int32_t kind, int32_t topk, float* scores_dev,
                    int32_t* idx_dev, float* prob_dev, void* stream) {
   if (!h) return MCM_EINVAL;
-  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC)
-    return fail(h, MCM_EINVAL, "unknown pixel_format");
+  if (int rc = check_pixel_format(h, pixel_format)) return rc;
   int rc = check_topk_call(h, text_feat_dev, B, K, T, kind, topk, scores_dev, idx_dev);
   if (rc) return rc;
   if ((rc = encode_image_impl(h, pixels_dev, pixel_format == MCM_PIXELS_U8_NHWC, B, h->feat, stream, true, x2 != 0)))
@@ -1659,7 +1663,7 @@ int mcm_debug_op_attention_split_hd(mcm_handle* h, const void* qkv_dev, void* ou
 // a pad column that is not written as zero, or a CLS row read instead of synthesised, shows as a NaN.
 int mcm_debug_vision_front(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t x2, int32_t B, int32_t stage,
                            int32_t poison, float* resid_out_dev, void* ln_out_dev, void* stream) {
-  if (pixel_format != MCM_PIXELS_F32_NCHW && pixel_format != MCM_PIXELS_U8_NHWC) return fail(h, MCM_EINVAL, "unknown pixel_format");
+  if (int rc = check_pixel_format(h, pixel_format)) return rc;
   int rc = check_image_call(h, pixels_dev, resid_out_dev, B, x2 != 0);
   if (rc) return rc;
   if (stage < 0 || stage > 1 || (stage == 1 && !ln_out_dev)) return fail(h, MCM_EINVAL, "stage 0 or 1; stage 1 needs ln_out_dev");

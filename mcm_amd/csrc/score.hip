@@ -373,11 +373,11 @@ hipError_t launch_score(const float* img, int B, const float* text, int K, int P
   if (B <= 0 || K <= 0 || P % 4 || kind < 0 || kind > MCM_SCORE_VAR || !(T > 0.f))
     return hipErrorInvalidValue;
   const int lds = (P + K) * (int)sizeof(float);
-  return launch_lds<score_kernel<false>, 150 * 1024>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, 0,
+  return launch_lds<score_kernel<false>, MCM_SCORE_LDS_MAX_BYTES>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, 0,
                                                      (int*)nullptr, (float*)nullptr);
 }
 
-bool score_shape_ok(int K, int P) { return K > 0 && P > 0 && P % 4 == 0 && (int64_t)(P + (int64_t)K) * 4 <= 150 * 1024; }
+bool score_shape_ok(int K, int P) { return K > 0 && P > 0 && P % 4 == 0 && (int64_t)(P + (int64_t)K) * 4 <= MCM_SCORE_LDS_MAX_BYTES; }
 
 hipError_t launch_score_topk(const float* img, int B, const float* text, int K, int P, float T, int kind,
                              int topk, float* scores, int* idx, float* prob, hipStream_t s) {
@@ -385,6 +385,6 @@ hipError_t launch_score_topk(const float* img, int B, const float* text, int K, 
       topk > MCM_TOPK_MAX || !scores || !idx)
     return hipErrorInvalidValue;
   const int lds = (P + K) * (int)sizeof(float);
-  return launch_lds<score_kernel<true>, 150 * 1024>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, topk, idx,
+  return launch_lds<score_kernel<true>, MCM_SCORE_LDS_MAX_BYTES>(dim3(B), dim3(NWV * 64), lds, s, img, text, K, P, T, kind, scores, topk, idx,
                                                     prob);
 }

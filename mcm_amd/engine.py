@@ -18,6 +18,7 @@ There is no CPU or eager fallback — a missing library or GPU raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Dict, Optional
 
@@ -38,6 +39,7 @@ HARNESS_ONLY_SYMBOLS = list(abi.HARNESS_PROTOTYPES)
 KERNEL_CLASSES = [name[len("MCM_KC_"):].lower() for name in sorted(abi.DEFINES, key=abi.DEFINES.get)
                   if name.startswith("MCM_KC_") and name != "MCM_KC_COUNT"]
 TOPK_MAX = abi.DEFINES["MCM_TOPK_MAX"]  # concepts the top-k scoring tail returns per image
+MAX_SPLITS = abi.DEFINES["MCM_KNN_MAX_SPLITS"]  # ranges a bank-streamed score cuts its bank into, at most
 
 _libs = {}
 
@@ -76,6 +78,23 @@ def _stream_ptr():
     import torch
 
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _pixel_format(px) -> int:
+    """MCM_PIXELS_* of pixels as `NativeCLIP._pixels` returns them."""
+    import torch
+
+    return abi.DEFINES["MCM_PIXELS_U8_NHWC" if px.dtype == torch.uint8 else "MCM_PIXELS_F32_NCHW"]
+
+
+def _int32_ids(a):
+    """[K,S] token ids or slots, tensor or array, as a contiguous int32 host array."""
+    return np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a), dtype=np.int32)
+
+
+def _at(t, s, n):
+    """The pointer of rows [s, s + n) of an optional output tensor: None where there is none."""
+    return None if t is None else t[s:s + n].data_ptr()
 
 
 class NativeCLIP:
@@ -174,6 +193,17 @@ class NativeCLIP:
         for s in range(0, b, nb):
             yield s, min(nb, b - s)
 
+    def _in_chunks(self, b, nb, call):
+        """call(start, n) -> rc over the chunks of at most nb that b images go through a fixed workspace in."""
+        for s, n in self._chunks(b, nb):
+            self._check(call(s, n))
+
+    def _empty(self, *shape, dtype=None, when=True):
+        """An uninitialised device tensor (fp32 unless `dtype`), or None for an output nobody asked for (`when` false)."""
+        import torch
+
+        return torch.empty(shape, device=self.device, dtype=dtype or torch.float32) if when else None
+
     def _x2_batch(self):
         """`x2_max_batch` where the split-activation arm exists."""
         nb = self.x2_max_batch
@@ -188,22 +218,17 @@ class NativeCLIP:
         so unmodified reference code that normalises (or, for the Mahalanobis baseline, deliberately
         does not normalise) the rows itself gets what it expects (utils/detection_util.py:158,187,225).
         `normalize=True` fuses the reference's `/= norm` (:226) into the pooling kernel."""
-        import torch
-
         if self.x2_default:
             return self.get_image_features_x2(pixel_values, normalize=normalize)
         px = self._pixels(pixel_values)
-        out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        return self._encode_into(px, out, normalize, x2=False)
+        return self._encode_into(px, self._empty(px.shape[0], self.geo.proj_dim), normalize, x2=False)
 
     def _encode_into(self, px, out, normalize: bool, x2: bool):
         """The image tower over `px` (as `_pixels` returns them) into out [b,P], in chunks of the arm's largest batch."""
-        import torch
-
-        fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
+        fmt = _pixel_format(px)
         fn = self._lib.mcm_encode_image_x2 if x2 else self._lib.mcm_encode_image_ex
-        for s, n in self._chunks(px.shape[0], self._x2_batch() if x2 else self.max_batch):
-            self._check(fn(self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)), out[s:s + n].data_ptr(), _stream_ptr()))
+        self._in_chunks(px.shape[0], self._x2_batch() if x2 else self.max_batch, lambda s, n: fn(
+            self._h, px[s:s + n].data_ptr(), fmt, n, int(bool(normalize)), out[s:s + n].data_ptr(), _stream_ptr()))
         return out
 
     def get_image_features_raw(self, pixel_values):
@@ -268,18 +293,17 @@ class NativeCLIP:
         result does not depend on it).  `return_values=True`: (scores, topv [B,k]), the k largest similarities, descending,
         -inf where the bank has no candidate left.  The workspace is a buffer of this object that grows on demand; queries
         go through in blocks of at most 4096 rows."""
-        import torch
-
         f, bk = self._bank_operands(features, bank)
         k, splits = int(k), int(splits)
-        B, N = int(f.shape[0]), int(bk.shape[0])
-        scores = torch.empty(B, device=self.device, dtype=torch.float32)
-        topv = torch.empty((B, max(k, 0)), device=self.device, dtype=torch.float32) if return_values else None
-        self._bank_score("_knn_work", B, lambda n, need: self._check_knn(
-            self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, need), n, N, k, splits),
-            lambda s, n, work: self._check(self._lib.mcm_knn_score_features(
+        B, N, max_k = int(f.shape[0]), int(bk.shape[0]), abi.DEFINES["MCM_KNN_MAX_K"]
+        scores, topv = self._empty(B), self._empty(B, max(k, 0), when=return_values)
+        self._bank_score(
+            "knn_scores", "_knn_work", B,
+            lambda n: self._rules(B=n, N=N, splits=splits) + [(f"k={k} (1 <= k <= {max_k})", not 1 <= k <= max_k)],
+            lambda n, need: self._lib.mcm_knn_workspace_bytes(self._h, n, N, k, splits, need),
+            lambda s, n, work: self._lib.mcm_knn_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), N, k, splits, work.data_ptr(), work.numel() * 4,
-                scores[s:s + n].data_ptr(), topv[s:s + n].data_ptr() if return_values else None, _stream_ptr())))
+                scores[s:s + n].data_ptr(), _at(topv, s, n), _stream_ptr()))
         return (scores, topv) if return_values else scores
 
     def _bank_operands(self, features, bank):
@@ -293,27 +317,46 @@ class NativeCLIP:
             raise ValueError(f"features and bank must be [*, {P}], got {tuple(f.shape)} and {tuple(bk.shape)}")
         return f, bk
 
-    def _bank_score(self, slot, B, ask, launch):
-        """The B queries of a bank-streamed score in blocks of at most 4096 rows: ask(n, byref(int64)) asks the library what a
-        block of n needs (and raises where it refuses), launch(start, n, work) scores the block.  `work` is the buffer kept in
-        the attribute `slot`, replaced by a larger one where it is too small: one buffer per score, since two scores may be in
-        flight on two streams."""
-        import torch
-
-        work = getattr(self, slot, None)
+    def _bank_score(self, what, slot, B, rules, ask, launch):
+        """The B queries of a bank-streamed score in blocks of at most 4096 rows: ask(n, byref(int64)) -> rc asks the library
+        what a block of n needs, launch(start, n, work) -> rc scores the block on the workspace of `slot`; rules(n) are the
+        score's rules for a block of n, by which `_refusal` explains a refused call."""
         for s in range(0, max(B, 1), 4096):
             n = min(4096, B - s)
-            need = ctypes.c_int64(0)
-            ask(n, ctypes.byref(need))
-            if work is None or work.numel() * 4 < need.value:
-                work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
-                setattr(self, slot, work)
-            launch(s, n, work)
+            work = self._workspace(slot, lambda need: self._refusal(what, ask(n, need), rules(n)))
+            self._refusal(what, launch(s, n, work), rules(n))
 
-    def _check_knn(self, rc, B, N, k, splits):
-        if rc:
-            raise ValueError(f"knn_scores: refused (rc={rc}) for B={B}, N={N}, k={k}, splits={splits}: B >= 1, N >= 1, "
-                             "1 <= k <= 1024, 0 <= splits <= 32 and proj_dim % 4 == 0 are required")
+    def _workspace(self, slot, ask):
+        """The workspace of a score: the buffer kept in the attribute `slot`, replaced by a larger one where it holds less
+        than ask(byref(int64)) says the call needs.  One buffer per score, since two scores may be in flight on two streams."""
+        need = ctypes.c_int64(0)
+        ask(ctypes.byref(need))
+        work = getattr(self, slot, None)
+        if work is None or work.numel() * 4 < need.value:
+            work = self._empty((need.value + 3) // 4)
+            setattr(self, slot, work)
+        return work
+
+    def _rules(self, T=None, splits=None, **at_least_1):
+        """The rules the bank-streamed scores share, as `_refusal` reads them: every keyword at least 1, T positive and
+        finite, splits within the header's range (either where given), and the walk's proj_dim % 4 == 0."""
+        P = self.geo.proj_dim
+        rules = [(f"{name}={v} ({name} >= 1)", v < 1) for name, v in at_least_1.items()]
+        if T is not None:
+            rules.append((f"T={T} (positive and finite)", not (T > 0 and math.isfinite(T))))
+        if splits is not None:
+            rules.append((f"splits={splits} (0 <= splits <= {MAX_SPLITS})", not 0 <= splits <= MAX_SPLITS))
+        return rules + [(f"proj_dim={P} (proj_dim % 4 == 0)", P % 4 != 0)]
+
+    def _refusal(self, what, rc, rules):
+        """The one path of a bank-streamed score's return code.  MCM_EINVAL is a refusal of the arguments: ValueError naming
+        the violated ones of `rules`, (text, violated) pairs with text = "name=value (the rule)"; where none is, every value
+        and the library's own message.  Any other failure is not about the arguments: RuntimeError through `_check`."""
+        if rc != abi.DEFINES["MCM_EINVAL"]:
+            return self._check(rc)
+        bad = [text for text, violated in rules if violated]
+        raise ValueError(f"{what}: refused (rc={rc}): " + ("; ".join(bad) if bad else
+                         ", ".join(text.split(" (")[0] for text, _ in rules) + ": " + self._lib.mcm_last_error(self._h).decode()))
 
     def neglabel_scores(self, features, bank, n_id, groups, group_size, T: float = 0.01, splits: int = 0,
                         return_groups: bool = False):
@@ -323,29 +366,22 @@ class NativeCLIP:
         choice, n = the bank in exactly n ranges (results agree across it to rounding, and are the same bits for a fixed
         value).  `return_groups=True`: (scores, S [B,groups]).  The workspace is a buffer of this object that grows on
         demand; queries go through in blocks of at most 4096 rows."""
-        import torch
-
         f, bk = self._bank_operands(features, bank)
         K, G, gs, splits, T = int(n_id), int(groups), int(group_size), int(splits), float(T)
         if K < 1 or G < 1 or gs < 1 or bk.shape[0] != K + G * gs:
             raise ValueError(f"neglabel_scores: the bank has {bk.shape[0]} rows, n_id + groups * group_size = {K} + {G} * {gs}")
-        B = int(f.shape[0])
-        scores = torch.empty(B, device=self.device, dtype=torch.float32)
-        grp = torch.empty((B, G), device=self.device, dtype=torch.float32) if return_groups else None
-        self._bank_score("_neg_work", B, lambda n, need: self._check_neglabel(
-            self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, need), n, K, G, gs, T, splits),
-            lambda s, n, work: self._check_neglabel(self._lib.mcm_neglabel_score_features(
+        B, max_g = int(f.shape[0]), abi.DEFINES["MCM_NEG_MAX_GROUPS"]
+        scores, grp = self._empty(B), self._empty(B, G, when=return_groups)
+        self._bank_score(
+            "neglabel_scores", "_neg_work", B,
+            lambda n: self._rules(B=n, n_id=K, group_size=gs, T=T, splits=splits) + [
+                (f"groups={G} (1 <= groups <= {max_g})", not 1 <= G <= max_g),
+                (f"n_id + groups * group_size = {K + G * gs} (at most 2^31 - 1)", K + G * gs > 2 ** 31 - 1)],
+            lambda n, need: self._lib.mcm_neglabel_workspace_bytes(self._h, n, K, G, gs, splits, need),
+            lambda s, n, work: self._lib.mcm_neglabel_score_features(
                 self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, G, gs, T, splits, work.data_ptr(), work.numel() * 4,
-                scores[s:s + n].data_ptr(), grp[s:s + n].data_ptr() if return_groups else None, _stream_ptr()),
-                n, K, G, gs, T, splits))
+                scores[s:s + n].data_ptr(), _at(grp, s, n), _stream_ptr()))
         return (scores, grp) if return_groups else scores
-
-    def _check_neglabel(self, rc, B, K, G, gs, T, splits):
-        if rc == -1:
-            raise ValueError(f"neglabel_scores: refused (rc={rc}) for B={B}, n_id={K}, groups={G}, group_size={gs}, T={T}, "
-                             f"splits={splits}: B, n_id, group_size >= 1, 1 <= groups <= 1024, T > 0 and finite, "
-                             "0 <= splits <= 32 and proj_dim % 4 == 0 are required")
-        self._check(rc)
 
     def vim_scores(self, features, bank, n_id, T: float = 0.01, alpha: float = 1.0, off=None, splits: int = 0,
                    return_parts: bool = False):
@@ -370,31 +406,17 @@ class NativeCLIP:
             if o.shape != (R,):
                 raise ValueError(f"vim_scores: off must hold R = {R} values, got {tuple(o.shape)}")
         B = int(f.shape[0])
-        scores = torch.empty(B, device=self.device, dtype=torch.float32)
-        parts = torch.empty((B, 3), device=self.device, dtype=torch.float32) if return_parts else None
-        self._bank_score("_vim_work", B, lambda n, need: self._check_vim(
-            self._lib.mcm_vim_workspace_bytes(self._h, n, K, R, splits, need), n, K, R, T, alpha, splits),
-            lambda s, n, work: self._check_vim(self._lib.mcm_vim_score_features(
-                self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, R, o.data_ptr() if o is not None else None, T, alpha,
-                splits, work.data_ptr(), work.numel() * 4, scores[s:s + n].data_ptr(),
-                parts[s:s + n].data_ptr() if return_parts else None, _stream_ptr()), n, K, R, T, alpha, splits))
-        return (scores, parts) if return_parts else scores
-
-    def _check_vim(self, rc, B, K, R, T, alpha, splits):
-        if rc == -1:
-            import math
-
-            bad = [what for what, wrong in (
-                (f"B={B} (B >= 1)", B < 1), (f"n_id={K} (n_id >= 1)", K < 1), (f"R={R} (R >= 1)", R < 1),
+        scores, parts = self._empty(B), self._empty(B, 3, when=return_parts)
+        self._bank_score(
+            "vim_scores", "_vim_work", B,
+            lambda n: self._rules(B=n, n_id=K, R=R, T=T, splits=splits) + [
                 (f"n_id + R = {K + R} (at most 2^31 - 1)", K + R > 2 ** 31 - 1),
-                (f"T={T} (positive and finite)", not (T > 0 and math.isfinite(T))),
-                (f"alpha={alpha} (finite)", not math.isfinite(alpha)),
-                (f"splits={splits} (0 <= splits <= 32)", not 0 <= splits <= 32),
-                (f"proj_dim={self.geo.proj_dim} (proj_dim % 4 == 0)", self.geo.proj_dim % 4 != 0)) if wrong]
-            raise ValueError(f"vim_scores: refused (rc={rc}): " + ("; ".join(bad) if bad else
-                             f"B={B}, n_id={K}, R={R}, T={T}, alpha={alpha}, splits={splits}: "
-                             + self._lib.mcm_last_error(self._h).decode()))
-        self._check(rc)
+                (f"alpha={alpha} (finite)", not math.isfinite(alpha))],
+            lambda n, need: self._lib.mcm_vim_workspace_bytes(self._h, n, K, R, splits, need),
+            lambda s, n, work: self._lib.mcm_vim_score_features(
+                self._h, f[s:s + n].data_ptr(), n, bk.data_ptr(), K, R, _at(o, 0, R), T, alpha, splits, work.data_ptr(),
+                work.numel() * 4, scores[s:s + n].data_ptr(), _at(parts, s, n), _stream_ptr()))
+        return (scores, parts) if return_parts else scores
 
     # -- GL-MCM: the local (patch-level) term next to MCM (include/mcm.h mcm_score_glmcm) -------------------
     @property
@@ -410,17 +432,13 @@ class NativeCLIP:
         """[b,3,S,S] fp32 (or [b,S,S,3] uint8) → (global [b,P], local [b,R,P]) fp32, unit-norm rows: the global feature of
         `get_image_features(..., normalize=True)` (the same bits) and, per patch token, the last layer's value path
         (layer_norm1 → v_proj → out_proj → post_layernorm → visual_projection; include/mcm.h mcm_encode_image_local)."""
-        import torch
-
         self._no_x2_local("get_local_features")
         px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0
+        fmt = _pixel_format(px)
         b, R, P = px.shape[0], self.local_rows, self.geo.proj_dim
-        glob = torch.empty((b, P), device=self.device, dtype=torch.float32)
-        loc = torch.empty((b, R, P), device=self.device, dtype=torch.float32)
-        for s, n in self._chunks(b, self.max_batch):
-            self._check(self._lib.mcm_encode_image_local(self._h, px[s:s + n].data_ptr(), fmt, n, glob[s:s + n].data_ptr(),
-                                                         loc[s:s + n].data_ptr(), _stream_ptr()))
+        glob, loc = self._empty(b, P), self._empty(b, R, P)
+        self._in_chunks(b, self.max_batch, lambda s, n: self._lib.mcm_encode_image_local(
+            self._h, px[s:s + n].data_ptr(), fmt, n, glob[s:s + n].data_ptr(), loc[s:s + n].data_ptr(), _stream_ptr()))
         return glob, loc
 
     def local_scores(self, local, text_features, T: float = 1.0, return_patches: bool = False):
@@ -434,45 +452,30 @@ class NativeCLIP:
         if loc.dim() != 3 or loc.shape[2] != self.geo.proj_dim or loc.shape[0] == 0 or loc.shape[1] == 0:
             raise ValueError(f"local must be [B,R,{self.geo.proj_dim}] with B, R >= 1, got {tuple(loc.shape)}")
         B, R, K, T = int(loc.shape[0]), int(loc.shape[1]), int(t.shape[0]), float(T)
-        need = ctypes.c_int64(0)
-        self._check_local(self._lib.mcm_local_workspace_bytes(self._h, B, R, K, ctypes.byref(need)), B, R, K, T)
-        work = getattr(self, "_local_work", None)
-        if work is None or work.numel() * 4 < need.value:
-            work = self._local_work = torch.empty((need.value + 3) // 4, device=self.device, dtype=torch.float32)
-        scores = torch.empty(B, device=self.device, dtype=torch.float32)
-        patch = torch.empty((B, R), device=self.device, dtype=torch.float32) if return_patches else None
-        self._check_local(self._lib.mcm_local_score_features(
+        rules = self._rules(B=B, R=R, K=K, T=T) + [(f"B R = {B * R} (below 2^31)", B * R > 2 ** 31 - 1)]
+        work = self._workspace("_local_work", lambda need: self._refusal(
+            "local_scores", self._lib.mcm_local_workspace_bytes(self._h, B, R, K, need), rules))
+        scores, patch = self._empty(B), self._empty(B, R, when=return_patches)
+        self._refusal("local_scores", self._lib.mcm_local_score_features(
             self._h, loc.data_ptr(), B, R, t.data_ptr(), K, T, work.data_ptr(), work.numel() * 4, scores.data_ptr(),
-            patch.data_ptr() if return_patches else None, _stream_ptr()), B, R, K, T)
+            _at(patch, 0, B), _stream_ptr()), rules)
         return (scores, patch) if return_patches else scores
-
-    def _check_local(self, rc, B, R, K, T):
-        if rc == -1:
-            raise ValueError(f"local_scores: refused (rc={rc}) for B={B}, R={R}, K={K}, T={T}: B, R, K >= 1, B R < 2^31, "
-                             "T > 0 and finite and proj_dim % 4 == 0 are required")
-        self._check(rc)
 
     def score_images_glmcm(self, pixel_values, text_features, T: float = 1.0, lam: float = 1.0, return_parts: bool = False):
         """pixels + pre-encoded bank [K,P] → the GL-MCM score [b] fp32 on the device: -(S_G + lam S_L), S_G the MCM term of
         the global feature (the bits of `score_images(..., "MCM")`), S_L the local term of `local_scores` on this image's
         patch rows (include/mcm.h mcm_score_glmcm); larger = more OOD.  `return_parts=True`: (scores, -S_G [b], -S_L [b],
         patch [b,R])."""
-        import torch
-
         self._no_x2_local("score_images_glmcm")
         px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0
+        fmt = _pixel_format(px)
         t = self._bank(text_features)
         b, R = px.shape[0], self.local_rows
-        out = torch.empty(b, device=self.device, dtype=torch.float32)
-        gs = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
-        ls = torch.empty(b, device=self.device, dtype=torch.float32) if return_parts else None
-        patch = torch.empty((b, R), device=self.device, dtype=torch.float32) if return_parts else None
-        for s, n in self._chunks(b, self.max_batch):
-            self._check(self._lib.mcm_score_glmcm(
-                self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T), float(lam), out[s:s + n].data_ptr(),
-                gs[s:s + n].data_ptr() if return_parts else None, ls[s:s + n].data_ptr() if return_parts else None,
-                patch[s:s + n].data_ptr() if return_parts else None, _stream_ptr()))
+        out = self._empty(b)
+        gs, ls, patch = (self._empty(*shape, when=return_parts) for shape in ((b,), (b,), (b, R)))
+        self._in_chunks(b, self.max_batch, lambda s, n: self._lib.mcm_score_glmcm(
+            self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T), float(lam), out[s:s + n].data_ptr(),
+            _at(gs, s, n), _at(ls, s, n), _at(patch, s, n), _stream_ptr()))
         return (out, gs, ls, patch) if return_parts else out
 
     def get_text_features(self, input_ids, attention_mask=None, normalize: bool = False):
@@ -482,8 +485,7 @@ class NativeCLIP:
         EOS, so pads never influence it (golden KAT)."""
         import torch
 
-        ids = np.ascontiguousarray(input_ids.detach().cpu().numpy() if hasattr(input_ids, "detach")
-                                   else np.asarray(input_ids), dtype=np.int32)
+        ids = _int32_ids(input_ids)
         if ids.ndim != 2:
             raise ValueError("input_ids must be [K,S]")
         K, S = ids.shape
@@ -502,10 +504,8 @@ class NativeCLIP:
         per prompt); it is widened exactly to fp32.  Returns [K,P] fp32, unit-norm rows with `normalize=True`."""
         import torch
 
-        ids = np.ascontiguousarray(input_ids.detach().cpu().numpy() if hasattr(input_ids, "detach")
-                                   else np.asarray(input_ids), dtype=np.int32)
-        slot = np.ascontiguousarray(slots.detach().cpu().numpy() if hasattr(slots, "detach")
-                                    else np.asarray(slots), dtype=np.int32)
+        ids = _int32_ids(input_ids)
+        slot = _int32_ids(slots)
         if ids.ndim != 2 or slot.shape != ids.shape:
             raise ValueError("input_ids and slots must both be [K,S]")
         K, S = ids.shape
@@ -542,23 +542,18 @@ class NativeCLIP:
 
         if not 1 <= int(topk) <= TOPK_MAX:
             raise ValueError(f"topk must be 1..{TOPK_MAX} (0: scores only), got {topk}")
-        return (torch.empty(b, device=self.device, dtype=torch.float32),
-                torch.empty((b, int(topk)), device=self.device, dtype=torch.int32),
-                torch.empty((b, int(topk)), device=self.device, dtype=torch.float32))
+        return self._empty(b), self._empty(b, int(topk), dtype=torch.int32), self._empty(b, int(topk))
 
     def _score_images_topk(self, pixel_values, text_features, T, score, topk, x2: bool):
         """`score_images` / `score_images_x2` with the top-k tail (mcm_score_topk), in chunks of the arm's largest batch."""
-        import torch
-
         nb = self._x2_batch() if x2 else self.max_batch
         px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
+        fmt = _pixel_format(px)
         t = self._bank(text_features)
         out, idx, prob = self._topk_out(px.shape[0], topk)
-        for s, n in self._chunks(px.shape[0], nb):
-            self._check(self._lib.mcm_score_topk(self._h, px[s:s + n].data_ptr(), fmt, int(x2), n, t.data_ptr(), t.shape[0],
-                                                 float(T), SCORE_KINDS[score], int(topk), out[s:s + n].data_ptr(),
-                                                 idx[s:s + n].data_ptr(), prob[s:s + n].data_ptr(), _stream_ptr()))
+        self._in_chunks(px.shape[0], nb, lambda s, n: self._lib.mcm_score_topk(
+            self._h, px[s:s + n].data_ptr(), fmt, int(x2), n, t.data_ptr(), t.shape[0], float(T), SCORE_KINDS[score], int(topk),
+            out[s:s + n].data_ptr(), idx[s:s + n].data_ptr(), prob[s:s + n].data_ptr(), _stream_ptr()))
         return out, idx, prob
 
     def score_features(self, image_features, text_features, T: float = 1.0, score: str = "MCM", topk: int = 0,
@@ -602,10 +597,11 @@ class NativeCLIP:
     # -- the streamed tail of the MCM family (include/mcm_score_stream.h) ---------------------------------
     def _streams(self, tail, K, splits, return_parts) -> bool:
         """Whether a call goes to the streamed tail.  "auto" sends it there exactly where the LDS tail refuses the shape
-        (csrc/score.hip score_shape_ok: (P + K) * 4 bytes of LDS above 150 KiB)."""
+        (csrc/score.hip score_shape_ok: (P + K) * 4 bytes of LDS above include/mcm.h MCM_SCORE_LDS_MAX_BYTES, 150 KiB)."""
         if tail not in ("auto", "lds", "stream"):
             raise ValueError(f"tail must be 'auto', 'lds' or 'stream', got {tail!r}")
-        stream = tail == "stream" or (tail == "auto" and (self.geo.proj_dim + int(K)) * 4 > 150 * 1024)
+        lds_max = abi.DEFINES["MCM_SCORE_LDS_MAX_BYTES"]
+        stream = tail == "stream" or (tail == "auto" and (self.geo.proj_dim + int(K)) * 4 > lds_max)
         if not stream and (splits or return_parts):
             raise ValueError("splits and return_parts belong to the streamed tail: pass tail='stream'")
         return stream
@@ -614,8 +610,6 @@ class NativeCLIP:
         """The streamed tail over features f [b,P] and bank t [K,P] (both as the kernels read them).  Returns scores, or
         (scores, idx, prob) with topk > 0, with parts [b,5] appended where asked for.  The workspace is a buffer of this
         object that grows on demand; queries go through in blocks of at most 4096 rows."""
-        import torch
-
         if not getattr(self._lib, "_mcm_score_stream", False):  # the extension header's entries are bound where they are used
             abi.declare(self._lib, names=list(abi.EXTENSION_PROTOTYPES))
             self._lib._mcm_score_stream = True
@@ -623,49 +617,57 @@ class NativeCLIP:
         if topk:
             scores, idx, prob = self._topk_out(B, topk)
         else:
-            scores = torch.empty(B, device=self.device, dtype=torch.float32) if out is None else out
-            idx = prob = None
-        parts = torch.empty((B, 5), device=self.device, dtype=torch.float32) if return_parts else None
-        self._bank_score("_score_stream_work", B, lambda n, need: self._check_score_stream(
-            self._lib.mcm_score_stream_workspace_bytes(self._h, n, K, topk, splits, need), n, K, T, topk, splits),
-            lambda s, n, work: self._check_score_stream(self._lib.mcm_score_features_stream(
+            scores, idx, prob = self._empty(B) if out is None else out, None, None
+        parts = self._empty(B, 5, when=return_parts)
+        self._bank_score(
+            "score_features (streamed tail)", "_score_stream_work", B,
+            lambda n: self._rules(B=n, T=T, splits=splits) + [
+                (f"K={K} (1 <= K <= 2^31 - 1)", not 1 <= K <= 2 ** 31 - 1),
+                (f"topk={topk} (0 <= topk <= {TOPK_MAX})", not 0 <= topk <= TOPK_MAX)],
+            lambda n, need: self._lib.mcm_score_stream_workspace_bytes(self._h, n, K, topk, splits, need),
+            lambda s, n, work: self._lib.mcm_score_features_stream(
                 self._h, f[s:s + n].data_ptr(), n, t.data_ptr(), K, T, kind, topk, splits, work.data_ptr(), work.numel() * 4,
-                scores[s:s + n].data_ptr(), parts[s:s + n].data_ptr() if return_parts else None,
-                idx[s:s + n].data_ptr() if topk else None, prob[s:s + n].data_ptr() if topk else None, _stream_ptr()),
-                n, K, T, topk, splits))
+                scores[s:s + n].data_ptr(), _at(parts, s, n), _at(idx, s, n), _at(prob, s, n), _stream_ptr()))
         res = (scores, idx, prob) if topk else (scores,)
         res = res + (parts,) if return_parts else res
         return res if len(res) > 1 else res[0]
-
-    def _check_score_stream(self, rc, B, K, T, topk, splits):
-        if rc == -1:
-            import math
-
-            bad = [what for what, wrong in (
-                (f"B={B} (B >= 1)", B < 1), (f"K={K} (1 <= K <= 2^31 - 1)", not 1 <= K <= 2 ** 31 - 1),
-                (f"T={T} (positive and finite)", not (T > 0 and math.isfinite(T))),
-                (f"topk={topk} (0 <= topk <= {TOPK_MAX})", not 0 <= topk <= TOPK_MAX),
-                (f"splits={splits} (0 <= splits <= 32)", not 0 <= splits <= 32),
-                (f"proj_dim={self.geo.proj_dim} (proj_dim % 4 == 0)", self.geo.proj_dim % 4 != 0)) if wrong]
-            raise ValueError("score_features (streamed tail): refused (rc=-1): " + ("; ".join(bad) if bad else
-                             f"B={B}, K={K}, T={T}, topk={topk}, splits={splits}: " + self._lib.mcm_last_error(self._h).decode()))
-        self._check(rc)
 
     def _score_images_stream(self, pixel_values, t, T, score, out, topk, x2, splits, return_parts):
         """`score_images` / `score_images_x2` by the streamed tail: `get_image_features(normalize=True)` of the arm into a
         buffer of this object that grows on demand, then `_score_stream` on it — the bits of
         `score_features(get_image_features(pixel_values, normalize=True), ..., tail="stream")`."""
-        import torch
-
         if x2:
             self._x2_batch()
         px = self._pixels(pixel_values)
         b = px.shape[0]
         feat = getattr(self, "_score_stream_feat", None)
         if feat is None or feat.shape[0] < b:
-            feat = self._score_stream_feat = torch.empty((b, self.geo.proj_dim), device=self.device, dtype=torch.float32)
+            feat = self._score_stream_feat = self._empty(b, self.geo.proj_dim)
         self._encode_into(px, feat[:b], True, x2)
         return self._score_stream(feat[:b], t, T, score, topk, splits, return_parts, out=out)
+
+    def _score_images(self, pixel_values, text_features, T, score, out, topk, tail, splits, return_parts, x2: bool):
+        """The body of `score_images` (x2 false) and `score_images_x2` (x2 true), and the one place that decides which entry a
+        call takes: the image tower followed by the streamed tail where `_streams` says so, else mcm_score_topk with topk,
+        else mcm_score_x2 on the split-activation arm, else mcm_score_u8 or mcm_score by the pixels' format."""
+        t = self._bank(text_features)
+        if self._streams(tail, t.shape[0], splits, return_parts):
+            return self._score_images_stream(pixel_values, t, T, score, out, topk, x2, splits, return_parts)
+        if topk:
+            return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=x2)
+        nb = self._x2_batch() if x2 else self.max_batch
+        px = self._pixels(pixel_values)
+        fmt = _pixel_format(px)
+        if x2:
+            entry, form = self._lib.mcm_score_x2, (fmt,)
+        else:  # the handle's own arm has one entry per pixel format
+            entry, form = self._lib.mcm_score_u8 if fmt == abi.DEFINES["MCM_PIXELS_U8_NHWC"] else self._lib.mcm_score, ()
+        if out is None:
+            out = self._empty(px.shape[0])
+        self._in_chunks(px.shape[0], nb, lambda s, n: entry(
+            self._h, px[s:s + n].data_ptr(), *form, n, t.data_ptr(), t.shape[0], float(T), SCORE_KINDS[score],
+            out[s:s + n].data_ptr(), _stream_ptr()))
+        return out
 
     def score_images(self, pixel_values, text_features, T: float = 1.0, score: str = "MCM", out=None, topk: int = 0,
                      tail: str = "auto", splits: int = 0, return_parts: bool = False):
@@ -673,24 +675,7 @@ class NativeCLIP:
         iteration of the reference loop, utils/detection_util.py:223-248).  `topk` > 0: (scores, idx, prob) as
         `score_features` returns them (`out` is not used then).  `tail`, `splits`, `return_parts`: as `score_features`; past
         the LDS tail's bank size the call is the image tower followed by the streamed tail."""
-        import torch
-
-        if self.x2_default:
-            return self.score_images_x2(pixel_values, text_features, T, score, out=out, topk=topk, tail=tail, splits=splits,
-                                        return_parts=return_parts)
-        t = self._bank(text_features)
-        if self._streams(tail, t.shape[0], splits, return_parts):
-            return self._score_images_stream(pixel_values, t, T, score, out, topk, False, splits, return_parts)
-        if topk:
-            return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=False)
-        px = self._pixels(pixel_values)
-        fn = self._lib.mcm_score_u8 if px.dtype == torch.uint8 else self._lib.mcm_score
-        if out is None:
-            out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
-        for s, n in self._chunks(px.shape[0], self.max_batch):
-            self._check(fn(self._h, px[s:s + n].data_ptr(), n, t.data_ptr(), t.shape[0], float(T),
-                           SCORE_KINDS[score], out[s:s + n].data_ptr(), _stream_ptr()))
-        return out
+        return self._score_images(pixel_values, text_features, T, score, out, topk, tail, splits, return_parts, self.x2_default)
 
     # -- split-activation arm: the re-scorer of threshold refinement (include/mcm.h mcm_score_x2) ----------------------
     @property
@@ -709,31 +694,13 @@ class NativeCLIP:
         hi + lo pair of fp16 numbers — scores that agree with the exact-fp32 arm to fp32 round-off, at several times its
         speed.  Any number of images (chunks of `x2_max_batch`).  `topk` > 0: (scores, idx, prob), as `score_images`;
         `tail`, `splits`, `return_parts` too."""
-        import torch
-
-        t = self._bank(text_features)
-        if self._streams(tail, t.shape[0], splits, return_parts):
-            return self._score_images_stream(pixel_values, t, T, score, out, topk, True, splits, return_parts)
-        if topk:
-            return self._score_images_topk(pixel_values, text_features, T, score, topk, x2=True)
-        nb = self._x2_batch()
-        px = self._pixels(pixel_values)
-        fmt = 1 if px.dtype == torch.uint8 else 0  # MCM_PIXELS_U8_NHWC / MCM_PIXELS_F32_NCHW
-        if out is None:
-            out = torch.empty(px.shape[0], device=self.device, dtype=torch.float32)
-        for s, n in self._chunks(px.shape[0], nb):
-            self._check(self._lib.mcm_score_x2(self._h, px[s:s + n].data_ptr(), fmt, n, t.data_ptr(), t.shape[0], float(T),
-                                               SCORE_KINDS[score], out[s:s + n].data_ptr(), _stream_ptr()))
-        return out
+        return self._score_images(pixel_values, text_features, T, score, out, topk, tail, splits, return_parts, True)
 
     def get_image_features_x2(self, pixel_values, normalize: bool = False):
         """`get_image_features` through the split-activation arm (raw projected features unless `normalize`)."""
-        import torch
-
         self._x2_batch()
         px = self._pixels(pixel_values)
-        out = torch.empty((px.shape[0], self.geo.proj_dim), device=self.device, dtype=torch.float32)
-        return self._encode_into(px, out, normalize, x2=True)
+        return self._encode_into(px, self._empty(px.shape[0], self.geo.proj_dim), normalize, x2=True)
 
     def x2_scorer(self):
         """An object with this scorer's `score_images` signature that runs the split-activation arm (mcm_amd.refine.Rescorer)."""

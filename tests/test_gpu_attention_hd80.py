@@ -9,13 +9,13 @@ A split row is whole 64-column blocks, so the split form exists for heads x 80 a
 here, and 1 and 3 heads are refused without a launch (as are head_dim 96, L = 1026 and causal attention at 80).
 
 Each budget check prints "BUDGET attn-hd80-<mode> <worst max|got - ref| / budget>" (run with -s to collect them)."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from tests import attention_hd_budget as hb
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -45,8 +45,7 @@ def harness_net():
         print(f"BUDGET attn-hd80-{mode} worst {WORST[mode]:.3f}")
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _qkv(nseq, L, heads, seed, spike=None, spread=1.5):

@@ -5,12 +5,12 @@ tests/test_online_softmax_budget.py) over every (sequence, head) pair, with logi
 and the ceiling (L = 1026 is refused without a launch).
 
 Each budget check prints "BUDGET <what> <precision> <worst max|got - ref| / budget>" (run with -s to collect them)."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 from tests import online_softmax_budget as ob
 
 pytestmark = pytest.mark.gpu
@@ -47,18 +47,10 @@ def harness_net():
     net.close()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
-def _check(what, prec, got, ref, bud, where=""):
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} {prec} {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} {prec} {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+_check = gs.check_budget
 
 
 def _qkv(nseq, L, heads, seed, spike=None, spread=1.5):

@@ -21,6 +21,7 @@ import warnings
 import numpy as np
 import pytest
 
+from tests import gpu_scaffold as gs
 from tests import text_reference as tr
 
 pytestmark = pytest.mark.gpu
@@ -44,8 +45,7 @@ def _quiet():
         yield
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _vp(a):

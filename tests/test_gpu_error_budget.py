@@ -4,13 +4,12 @@ shapes the size policy actually routes (on sampled rows), the LayerNorm on hosti
 the shipped persistent form, and all five score kinds up to the largest bank launch_score accepts.
 
 Each check prints "BUDGET <kernel> <precision> <worst max|got - ref| / budget>" (run with -s to collect them)."""
-import ctypes
-import dataclasses
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -46,18 +45,10 @@ def harness_net():
     net.close()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
-def _check(what, prec, got, ref, bud, where=""):
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} {prec} {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} {prec} {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+_check = gs.check_budget
 
 
 # ---- GEMM --------------------------------------------------------------------------------------------------------------
@@ -301,15 +292,6 @@ def test_attention_forced_persistent_within_budget(harness_net, nseq, L, heads, 
 
 
 # ---- scores ------------------------------------------------------------------------------------------------------------
-def _score_net(P):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 def _kmax(P):
     """The largest bank launch_score accepts (score.hip: (P + K) * 4 bytes of LDS <= 150 KiB)."""
     return 150 * 1024 // 4 - P
@@ -319,7 +301,7 @@ def _kmax(P):
 def test_scores_within_budget(P):
     from mcm_amd.config import SCORE_KINDS
 
-    net = _score_net(P)
+    net = gs.widened_net(P)
     try:
         B = 17
         for K in (1, 2, 1000, 21841, _kmax(P)):

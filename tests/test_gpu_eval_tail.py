@@ -6,7 +6,6 @@ Measures: AUROC and FPR are single fp64 divisions of exact integers on both side
 sum of n_pos terms and must be within eval_reference.aupr_bound(n_pos).  -inf / +inf are ordered scores; a NaN anywhere makes
 all three outputs NaN (include/mcm.h).  Each measures case prints "BUDGET aupr fp64 <|d| / bound>", each Mahalanobis case
 "BUDGET maha fp64 <max |got - ref| / budget>" (run with -s to collect them)."""
-import dataclasses
 import math
 
 import numpy as np
@@ -14,35 +13,22 @@ import pytest
 
 from tests import error_budget as eb
 from tests import eval_reference as er
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
 
 INF = np.float32(np.inf)
 FLT_MAX = np.finfo(np.float32).max
 
 
-def _net(P=None):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P is not None and P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def net():
-    n = _net()
+    n = gs.widened_net()
     yield n
     n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
 def _check_measures(net, pos, neg, level=0.95, negate=False, where="", dev=None):
@@ -299,16 +285,7 @@ MAHA_WIDTHS = [64, 100, 512, 768]
 
 @pytest.fixture(scope="module")
 def maha_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
+    yield from gs.net_cache()
 
 
 @pytest.mark.parametrize("pkind", ["asym", "scaled"])

@@ -15,6 +15,7 @@ import pytest
 
 from tests import error_budget as eb
 from tests import gelu_budget as gb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -52,18 +53,10 @@ def harness_net():
     n.close()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
-def _check(what, mode, got, ref, bud, where=""):
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} {mode} {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} {mode} {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+_check = gs.check_budget
 
 
 # ---- the fc1 epilogue, operator level -------------------------------------------------------------------------------------

@@ -9,10 +9,13 @@ import numpy as np
 import pytest
 
 from tests import glmcm_budget as gb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
+_bits = gs.bits
 
 WIDTHS = [64, 512, 768, 1024]
 # (B, R, K).  (1,1,1): one cell; (3,16,5): three images inside one query tile; (2,196,300): images across three tile edges, K
@@ -22,42 +25,14 @@ SHAPES = [(1, 1, 1), (3, 16, 5), (2, 196, 300), (5, 49, 257), (65, 3, 256), (1, 
 TEMPS = [1.0, 0.01]
 
 
-def _net(P):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def gl_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    yield from gs.net_cache()
 
 
 def _run(net, local, text, T):
     s, p = net.local_scores(local, text, T=T, return_patches=True)
     return s.cpu().numpy(), p.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 @pytest.mark.parametrize("P", WIDTHS)

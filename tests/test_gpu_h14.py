@@ -10,13 +10,14 @@ score (bars 4 / 2), split-activation arm vs fp32 arm 9.3e-10 (bar 2e-9); H14-2L 
 fp32 7.5e-9, fp16 1.8e-7, x2 7.5e-9, bf16 2.9e-6; LayerNorm at 1280 within 1.000 (16-bit) / 0.24 of its budget, pool_project 0.007.
 The operator-level GEMM checks at the H/14 shapes, the vision front at D = 1280, the refined-FPR95 draw, GraphedScorer capture
 and the CLI run follow the tower tests."""
-import ctypes
+import functools
 import math
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -27,23 +28,14 @@ DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}
 D = 1280
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _check(what, mode, got, ref, bud, where=""):
-    assert np.isfinite(bud).all(), f"{what} {mode} {where}: a non-finite budget"
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} {mode} {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} {mode} {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+_check = functools.partial(gs.check_budget, finite_budget=True)
 
 
 @pytest.fixture(scope="module")

@@ -3,10 +3,11 @@ C ABI's operator-level entry points (include/mcm.h), against the CPU oracle on t
 seeded inputs.  bf16-mode comparisons feed the oracle the bf16-rounded operands, so the
 only differences left are fp32 accumulation order and the bf16 rounding of outputs.
 """
-import ctypes
 
 import numpy as np
 import pytest
+
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -59,8 +60,7 @@ def _dev(a, dtype=None):
     return t.to(dtype) if dtype is not None else t
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 @pytest.mark.parametrize("D", [128, 512, 768, 1024])
@@ -680,15 +680,11 @@ def test_fp16_layernorm_and_attention_saturate(tiny_net):
 def test_score_kinds_full_projection_dims(P, geo_name, K):
     """The scoring tail at the projection widths of the real checkpoints (512 for B/16 and B/32, 768 for
     L/14) and K = 1000, all five --score kinds, against the oracle (test_score_kinds covers the tiny P)."""
-    import dataclasses
-
-    from mcm_amd.config import SCORE_KINDS, geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
+    from mcm_amd.config import SCORE_KINDS
     from oracle import oracle as orc
 
-    geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-    net = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
+    net = gs.widened_net(P)
+    geo = net.geo
     try:
         rng = np.random.default_rng(K + P)
         B = 41

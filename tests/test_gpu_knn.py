@@ -3,17 +3,18 @@ tests/knn_budget.py — value for value on lattice inputs (every similarity exac
 inputs — its invariance, edge and refusal contract, a bank beyond 4 GiB, and get_knn_bank / get_knn_score / the CLI end to end.
 Budget cases print "BUDGET knn fp32 <worst ratio> ..." (run with -s to collect them)."""
 import ctypes
-import dataclasses
 import types
 
 import numpy as np
 import pytest
 
+from tests import gpu_scaffold as gs
 from tests import knn_budget as kb
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
 
 WIDTHS = [64, 512, 768, 1024]
 # one row; 63 / 65 and 255 / 257 rows: either side of a wave's 64 candidates and of the 256-row tile; 65 and 130 queries: a
@@ -23,33 +24,9 @@ KS = [1, 2, 63, 64, 65, 1000, 1024]
 SPLITS = [1, 2, 7]
 
 
-def _net(P):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def knn_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    yield from gs.net_cache()
 
 
 def _run(net, f, bank, k, splits=0):

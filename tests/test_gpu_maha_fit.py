@@ -2,51 +2,28 @@
 under tests/maha_fit_budget.py, its determinism / symmetry / refusal contract, and get_mean_prec_device end to end against the
 host route, the reference's own outputs (tests/golden/maha_tiny.npz) and through the CLI.  Each kernel case prints
 "BUDGET maha-fit fp64 <max |got - ref| / budget> ..." (run with -s to collect them)."""
-import dataclasses
 import os
 import types
 
 import numpy as np
 import pytest
 
+from tests import gpu_scaffold as gs
 from tests import maha_fit_budget as fb
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
 
 # proj_dim must be a multiple of 4 (mcm_create); the kernel's tile is 64 wide: 64 is one tile, 100 one full and one ragged,
 # 1024 sixteen (136 workgroups); the Mahalanobis widths of tests/test_gpu_eval_tail.py, and 1024
 WIDTHS = [64, 100, 512, 768, 1024]
 
 
-def _net(P, max_batch):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=max_batch, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def fit_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P, 512 if P == 512 else 72)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    yield from gs.net_cache(lambda P: gs.widened_net(P, max_batch=512 if P == 512 else 72))
 
 
 def _run(net, x, splits, shift):

@@ -3,17 +3,19 @@ budget of tests/neglabel_budget.py — the arithmetic term plus one ulp on latti
 full budget on unit inputs — its determinism, NaN and refusal contract, the method's own size, and mining, bank, scoring and the
 CLI end to end.  Budget cases print "BUDGET neglabel <worst ratio> ..." (run with -s to collect them)."""
 import ctypes
-import dataclasses
 import types
 
 import numpy as np
 import pytest
 
+from tests import gpu_scaffold  # (not "as gs": gs is the group size here)
 from tests import neglabel_budget as nb
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gpu_scaffold.dev
+_bits = gpu_scaffold.bits
 
 WIDTHS = [64, 512, 768, 1024]
 # (B, K, G, gs).  (1,1,1,1): two rows, so five of seven splits are empty; (3,300,1,1): the ID range across the tile edge at 256
@@ -25,42 +27,14 @@ SPLITS = [1, 2, 7, 0]
 TEMPS = [0.01, 1.0]
 
 
-def _net(P):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def neg_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    yield from gpu_scaffold.net_cache()
 
 
 def _run(net, f, bank, K, G, gs, T, splits=0):
     s, g = net.neglabel_scores(f, bank, K, G, gs, T=T, splits=splits, return_groups=True)
     return s.cpu().numpy(), g.cpu().numpy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 @pytest.mark.parametrize("P", WIDTHS)
@@ -209,7 +183,7 @@ def test_refused_calls_launch_nothing(neg_nets):
 def test_the_methods_own_size_against_torch_fp64():
     """B = 512, K = 1000, G = 100, gs = 100 (N = 11 000), P = 512, T = 0.01, the library choosing the splits: the fp64
     similarities and eps come from torch on the device."""
-    net = _net(512)
+    net = gpu_scaffold.widened_net(512)
     B, K, G, gs, T = 512, 1000, 100, 100, 0.01
     f, bank = nb.unit_case(B, K, G, gs, 512, seed=1)
     fd, bd = _dev(f), _dev(bank)

@@ -3,18 +3,20 @@ the derived budget of tests/score_stream_budget.py — the arithmetic term plus 
 in fp32), the full budget on unit inputs — against the LDS tail, its top-k order, determinism, NaN and refusal contract, and the
 engine's routing past the LDS tail's bank size.  Budget cases print "BUDGET score_stream <worst ratio> ..." (run with -s)."""
 import ctypes
-import dataclasses
 import types
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 from tests import score_stream_budget as sb
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
+_bits = gs.bits
 
 WIDTHS = [4, 36, 64, 512, 1024]   # 36: not a multiple of the walk's 32-column chunk
 # (B, K).  (1,1): one row, with 32 splits thirty-one of them are empty; (3,300): the bank across the tile edge, 32 splits of 10
@@ -27,37 +29,9 @@ TEMPS = [0.01, 1.0]
 K_CAP, P_CAP = 38337, 64          # the first K the LDS tail refuses at P = 64: (64 + 38337) * 4 = 150 KiB + 4
 
 
-def _net(P, **kw):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256, **kw)
-
-
 @pytest.fixture(scope="module")
 def nets():
-    made = {}
-
-    def get(P):
-        if P not in made:
-            made[P] = _net(P)
-        return made[P]
-
-    yield get
-    for n in made.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
+    yield from gs.net_cache()
 
 
 def _run(net, fd, bd, T, splits, kind="MCM", topk=0):
@@ -72,7 +46,7 @@ def _run(net, fd, bd, T, splits, kind="MCM", topk=0):
 
 
 def _same_bits(a, b, rows=slice(None), keys=sb.KINDS):
-    return all(np.array_equal(_bits(a[k][rows]), _bits(b[k][rows])) for k in keys)
+    return gs.same_bits(a, b, rows, keys)
 
 
 @pytest.mark.parametrize("P", WIDTHS)
@@ -311,7 +285,7 @@ def test_refused_calls_launch_nothing(nets):
 @pytest.fixture(scope="module")
 def cap():
     """(net, f, bank, fd, bd, s64): three planted unit queries against a unit bank of K_CAP rows, on tiny's own proj_dim."""
-    net = _net(P_CAP)
+    net = gs.widened_net(P_CAP)
     f, bank = sb.unit_case(3, K_CAP, P_CAP, seed=17)
     yield net, f, bank, _dev(f), _dev(bank), sb.similarities(f, bank)
     net.close()

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 from tests import online_softmax_budget as ob
 
 pytestmark = pytest.mark.gpu
@@ -56,8 +57,7 @@ def harness_net():
     n.close()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _dev(a):
@@ -65,13 +65,7 @@ def _dev(a):
 
 
 def _check(what, got, ref, bud, where=""):
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} split {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} split {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+    return gs.check_budget(what, "split", got, ref, bud, where)
 
 
 def _decode(bits, dtype):

@@ -7,11 +7,12 @@ fp32-valued weights (every kernel the size policy can pick), the policy (`auto` 
 a number of the operand dtype), the dtype argument of mcm_set_weight, and the towers in split mode against the HF
 fixtures and the exact-fp32 arm.
 """
-import ctypes
 import os
 
 import numpy as np
 import pytest
+
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -21,8 +22,7 @@ PREC = {"bf16": 0, "fp32": 1, "fp16": 2}
 DTYPE = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 @pytest.fixture(scope="module")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -72,16 +73,7 @@ def _bits(t):
 @pytest.fixture(scope="module")
 def nets():
     """One tiny-geometry handle per projection width (the tail's P is the handle's proj_dim)."""
-    import dataclasses
-
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    made = {}
-    for P in PS:
-        geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-        made[P] = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp32", max_batch=4, max_prompt_tokens=256)
+    made = {P: gs.widened_net(P, precision="fp32", max_batch=4) for P in PS}
     yield made
     for n in made.values():
         n.close()

@@ -10,12 +10,14 @@ discriminate on the CPU by tests/test_error_budget.py):
 
 Each budget check prints "BUDGET <family> <mode> <worst max|got - ref| / budget>" (run with -s to collect them)."""
 import ctypes
+import functools
 import dataclasses
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -27,23 +29,14 @@ EINVAL = -1
 PRE = "vision_model."
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _check(what, mode, got, ref, bud, where=""):
-    assert np.isfinite(bud).all(), f"{what} {mode} {where}: a non-finite budget"
-    r, i = eb.worst(got, ref, bud)
-    print(f"BUDGET {what} {mode} {r:.3f} {where}")
-    if r > 1.0:
-        idx = np.unravel_index(i, np.shape(ref))
-        pytest.fail(f"{what} {mode} {where}: max|got - ref| / budget = {r:.3g} at {idx}: got "
-                    f"{np.asarray(got).flat[i]!r} ref {ref.flat[i]!r} budget {bud.flat[i]:.3g}")
-    return r
+_check = functools.partial(gs.check_budget, finite_budget=True)
 
 
 # ---- handles -----------------------------------------------------------------------------------------------------------
@@ -469,12 +462,7 @@ def _bank_rows(K, T, P, seed):
 @pytest.mark.parametrize("P", [64, 512, 768])
 def test_bank_reduce_within_budget(P):
     """Unit template rows; class 0's templates nearly cancel (mean of norm ~ 1e-3): the budget scales with 1 / ||mean||."""
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-    net = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
+    net = gs.widened_net(P)
     try:
         for K in (1, 3, 1000, 1001):
             for T in (1, 7, 80):

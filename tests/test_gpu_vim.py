@@ -3,17 +3,19 @@ tests/vim_budget.py — the arithmetic term plus one ulp on lattice inputs (ever
 unit inputs — its off / parts / determinism / NaN / refusal contract, and fit, scoring and the CLI end to end.  Budget cases
 print "BUDGET vim <worst ratio> ..." (run with -s to collect them)."""
 import ctypes
-import dataclasses
 import types
 
 import numpy as np
 import pytest
 
+from tests import gpu_scaffold as gs
 from tests import vim_budget as vb
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+_dev = gs.dev
+_bits = gs.bits
 
 WIDTHS = [4, 36, 64, 512, 1024]   # 36: not a multiple of the walk's 32-column chunk
 # (B, K, R), N = K + R.  (1,1,1): two rows, with 32 splits thirty of them are empty; (3,300,1): the prompts across the tile edge
@@ -27,33 +29,9 @@ SPLITS = [1, 2, 3, 32]
 ALPHA = 1.75
 
 
-def _net(P):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("tiny")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"tiny-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
-
-
 @pytest.fixture(scope="module")
 def vim_nets():
-    nets = {}
-
-    def get(P):
-        if P not in nets:
-            nets[P] = _net(P)
-        return nets[P]
-
-    yield get
-    for n in nets.values():
-        n.close()
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    yield from gs.net_cache()
 
 
 def _run(net, f, bank, K, off=None, T=0.01, alpha=ALPHA, splits=0):
@@ -63,12 +41,8 @@ def _run(net, f, bank, K, off=None, T=0.01, alpha=ALPHA, splits=0):
     return {"score": s.cpu().numpy(), "resid": p[:, 0].copy(), "lse": p[:, 1].copy(), "maxlogit": p[:, 2].copy()}
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
 def _same_bits(a, b, rows=slice(None)):
-    return all(np.array_equal(_bits(a[k][rows]), _bits(b[k][rows])) for k in vb.OUTPUTS)
+    return gs.same_bits(a, b, rows, vb.OUTPUTS)
 
 
 @pytest.mark.parametrize("P", WIDTHS)

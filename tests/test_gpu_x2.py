@@ -3,12 +3,12 @@ activation as hi + lo fp16 pairs against the CPU oracle through the operator-lev
 the exact-fp32 arm of the same library.  The bar is fp32 round-off, not fp16's: a split operand carries ~22 significand bits.
 Reference arithmetic: HF modeling_clip.py:298-335 (attention), :346-350 (MLP), :362-383 (layer); the reference's tail
 utils/detection_util.py:225-248."""
-import ctypes
 
 import numpy as np
 import pytest
 
 from tests import error_budget as eb
+from tests import gpu_scaffold as gs
 
 pytestmark = pytest.mark.gpu
 
@@ -18,8 +18,7 @@ F16 = 2  # MCM_PREC_F16
 SPLIT_W, SPLIT_X, SPLIT_OUT = 1, 2, 4
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_ptr = gs.ptr
 
 
 def _dev(a, dtype=None):

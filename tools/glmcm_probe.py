@@ -15,29 +15,20 @@ One JSON object on stdout (and, with --out, in FILE)."""
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def _kernels_ms(stats):
-    return sum(v["ms"] for kc, v in stats.items() if not kc.startswith("gemm_"))  # (the gemm_* classes repeat launches of "gemm")
+from tools import probe_common as pc  # noqa: E402
 
 
 def step(batch, reps):
     import torch
 
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("ViT-B/16")
-    net = NativeCLIP(geo, synth_state_dict(geo, 0, regime="fp16-exact"), precision="fp16", max_batch=batch,
-                     synthetic_weights=True, x2_max_batch=-1)
-    P, K, T = geo.proj_dim, 1000, 1.0
+    net = pc.b16_handle(batch)
+    geo, (P, K, T) = net.geo, (net.geo.proj_dim, 1000, 1.0)
     g = torch.Generator(device="cuda").manual_seed(1)
     px = torch.randn((batch, 3, geo.image_size, geo.image_size), device="cuda", generator=g)
     prompts = torch.nn.functional.normalize(torch.randn((K, P), device="cuda", generator=g), dim=-1)
@@ -71,11 +62,11 @@ def step(batch, reps):
     assert tail["launches"] == reps, tail
     res = {"model": "ViT-B/16", "precision": "fp16", "B": batch, "R": net.local_rows, "K": K, "P": P, "T": T,
            "score_ms": s_ms / reps, "glmcm_ms": g_ms / reps, "glmcm_over_score": g_ms / s_ms,
-           "forward_kernels_ms": _kernels_ms(fwd) / reps, "local_pass_ms": (_kernels_ms(both) - _kernels_ms(fwd)) / reps,
+           "forward_kernels_ms": pc.kernels_ms(fwd) / reps, "local_pass_ms": (pc.kernels_ms(both) - pc.kernels_ms(fwd)) / reps,
            "local_pass_launches": (sum(v["launches"] for kc, v in both.items() if not kc.startswith("gemm_"))
                                    - sum(v["launches"] for kc, v in fwd.items() if not kc.startswith("gemm_"))) // reps,
            "local_tail_ms": tail["ms"] / reps, "local_tail_tflops_fp32": tail["flops"] / reps / (tail["ms"] / reps) / 1e9}
-    print("PROBE " + json.dumps(res), flush=True)
+    pc.emit(res)
     net.profile(False)
     net.close()
     return res
@@ -92,18 +83,11 @@ def main():
     if a.child:
         step(a.batch, a.reps)
         return 0
-    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--batch", str(a.batch),
-           "--reps", str(a.reps), "--child"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    lines = [ln[6:] for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
-    if r.returncode or len(lines) != 1:
-        print(f"the probe failed (exit {r.returncode})\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", file=sys.stderr)
-        return 1
-    print(lines[0], flush=True)
-    if a.out:
+    rc, results = pc.drive(__file__, [()], ["--batch", a.batch, "--reps", a.reps], a.limit, name=lambda s: "the probe")
+    if not rc and a.out:
         with open(a.out, "w") as fh:
-            json.dump(json.loads(lines[0]), fh, indent=1)
-    return 0
+            json.dump(results[0], fh, indent=1)
+    return rc
 
 
 if __name__ == "__main__":

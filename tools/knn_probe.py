@@ -11,14 +11,14 @@ and P = 512 (the ViT-B/16 projection width; fp16 handle), unit-norm seeded rows:
   score_step_ms     the kernels of one mcm_score step of the same handle at the same batch.
 One JSON object per (N, k) on stdout (and, with --out, all of them in FILE)."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools import probe_common as pc  # noqa: E402
 
 SIZES = [25_000, 250_000, 1_281_167]
 KS = [10, 200, 1000]
@@ -38,14 +38,8 @@ def _torch_route(f, bank, k):
 def step(N, batch, reps):
     import torch
 
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("ViT-B/16")
-    net = NativeCLIP(geo, synth_state_dict(geo, 0, regime="fp16-exact"), precision="fp16", max_batch=batch,
-                     synthetic_weights=True, x2_max_batch=-1)
-    P = geo.proj_dim
+    net = pc.b16_handle(batch)
+    geo, P = net.geo, net.geo.proj_dim
     g = torch.Generator(device="cuda").manual_seed(1)
     bank = torch.nn.functional.normalize(torch.randn((N, P), device="cuda", generator=g), dim=-1)
     f = torch.nn.functional.normalize(bank[torch.randint(0, N, (batch,), device="cuda", generator=g)]
@@ -59,30 +53,14 @@ def step(N, batch, reps):
     net.profile_read()
     for _ in range(reps):
         net.score_images(px, prompts, 1.0, "MCM")
-    st = net.profile_read()
-    step_ms = sum(v["ms"] for kc, v in st.items() if not kc.startswith("gemm_")) / reps
+    step_ms = pc.kernels_ms(net.profile_read()) / reps
     out = []
     for k in KS:
-        mine = net.knn_scores(f, bank, k)                     # warm-up of both routes, and they must agree
-        ref = _torch_route(f, bank, k)
-        torch.cuda.synchronize()
-        agree = float((mine - ref).abs().max())
-        net.profile_read()
-        t_ms, ev = 0.0, [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        for _ in range(reps):                                 # alternating
-            net.knn_scores(f, bank, k)
-            ev[0].record()
-            _torch_route(f, bank, k)
-            ev[1].record()
-            torch.cuda.synchronize()
-            t_ms += ev[0].elapsed_time(ev[1])
-        kn = net.profile_read()["score"]
-        assert kn["launches"] == reps, kn
-        res = {"N": N, "k": k, "B": batch, "P": P, "knn_launch_ms": kn["ms"] / reps, "torch_topk_ms": t_ms / reps,
-               "knn_over_torch": kn["ms"] / t_ms, "score_step_ms": step_ms, "knn_over_step": kn["ms"] / reps / step_ms,
-               "knn_tflops_fp32": kn["flops"] / reps / (kn["ms"] / reps) / 1e9, "max_abs_diff_vs_torch": agree}
-        print("PROBE " + json.dumps(res), flush=True)
-        out.append(res)
+        t = pc.agree_and_time(net, lambda: net.knn_scores(f, bank, k), lambda: _torch_route(f, bank, k), reps)
+        out.append(pc.emit({"N": N, "k": k, "B": batch, "P": P, "knn_launch_ms": t["ms"], "torch_topk_ms": t["yardstick_ms"],
+                            "knn_over_torch": t["ms"] / t["yardstick_ms"], "score_step_ms": step_ms,
+                            "knn_over_step": t["ms"] / step_ms, "knn_tflops_fp32": t["flops"] / t["ms"] / 1e9,
+                            "max_abs_diff_vs_torch": t["max_abs_diff"]}))
     net.profile(False)
     net.close()
     return out
@@ -99,22 +77,8 @@ def main():
     if a.child is not None:
         step(a.child, a.batch, a.reps)
         return 0
-    results = []
-    for N in SIZES:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--batch", str(a.batch),
-               "--reps", str(a.reps), "--child", str(N)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln[6:] for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
-        for ln in lines:
-            results.append(json.loads(ln))
-            print(ln, flush=True)
-        if a.out:
-            with open(a.out, "w") as fh:
-                json.dump(results, fh, indent=1)
-        if r.returncode or len(lines) != len(KS):
-            print(f"N = {N} failed (exit {r.returncode}); stopping\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", file=sys.stderr)
-            return 1
-    return 0
+    return pc.drive(__file__, [(N,) for N in SIZES], ["--batch", a.batch, "--reps", a.reps], a.limit, a.out, len(KS),
+                    lambda s: f"N = {s[0]}")[0]
 
 
 if __name__ == "__main__":

@@ -10,11 +10,8 @@ Runs every GPU step as a child process of its own under a time limit and stops a
              seeded synthetic ViT-B/16 images at --batch.
 One JSON object per step on stdout (and, with --out, all of them in FILE)."""
 import argparse
-import dataclasses
-import json
 import os
 import resource
-import subprocess
 import sys
 import time
 import types
@@ -23,23 +20,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def _handle(P, batch):
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = geometry("ViT-B/16")
-    if P != geo.proj_dim:
-        geo = dataclasses.replace(geo, name=f"ViT-B/16-P{P}", proj_dim=P)
-    return NativeCLIP(geo, synth_state_dict(geo, 0, regime="fp16-exact"), precision="fp16", max_batch=batch,
-                      synthetic_weights=True, x2_max_batch=-1)
+from tools import probe_common as pc  # noqa: E402
 
 
 def step_launch(P, batch, reps=20):
     import torch
 
-    net = _handle(P, batch)
+    net = pc.b16_handle(batch, P)
     g = torch.Generator(device="cuda").manual_seed(1)
     px = torch.randn((batch, 3, net.geo.image_size, net.geo.image_size), device="cuda", generator=g)
     bank = torch.nn.functional.normalize(torch.randn((1000, P), device="cuda", generator=g), dim=-1)
@@ -59,7 +46,7 @@ def step_launch(P, batch, reps=20):
     step = net.profile_read()
     net.profile(False)
     assert fit["launches"] == reps, fit
-    step_ms = sum(v["ms"] for k, v in step.items() if not k.startswith("gemm_")) / reps   # (the gemm_* sub-classes repeat "gemm")
+    step_ms = pc.kernels_ms(step) / reps
     fit_ms = fit["ms"] / reps
     net.close()
     return {"step": "launch", "P": P, "B": batch, "fit_launch_ms": fit_ms, "score_step_kernel_ms": step_ms,
@@ -72,7 +59,7 @@ def step_fit(route, images, batch, tdir):
     from mcm_amd.detection import get_mean_prec, get_mean_prec_device
     from mcm_amd.synth import DevicePatternLoader
 
-    net = _handle(512, batch)
+    net = pc.b16_handle(batch, 512)
     args = types.SimpleNamespace(n_cls=1000, feat_dim=512, model="CLIP", normalize=False, template_dir=tdir,
                                  in_dataset="ImageNet", max_count=250, batch_size=batch)
     fn = get_mean_prec_device if route == "device" else get_mean_prec
@@ -107,24 +94,11 @@ def main():
         else:
             with tempfile.TemporaryDirectory() as tdir:
                 res = step_fit(a.child[1], a.images, a.batch, tdir)
-        print("PROBE " + json.dumps(res), flush=True)
+        pc.emit(res)
         return 0
     steps = [["launch", "512"], ["launch", "768"], ["launch", "1024"], ["fit", "device"], ["fit", "host"]]
-    results = []
-    for st in steps:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--images", str(a.images),
-               "--batch", str(a.batch), "--child"] + st
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln[6:] for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
-        if r.returncode or not lines:
-            print(f"step {st} failed (exit {r.returncode}); stopping\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", file=sys.stderr)
-            break
-        results.append(json.loads(lines[-1]))
-        print(lines[-1], flush=True)
-        if a.out:
-            with open(a.out, "w") as f:
-                json.dump(results, f, indent=1)
-    return 0 if len(results) == len(steps) else 1
+    return pc.drive(__file__, steps, ["--images", a.images, "--batch", a.batch], a.limit, a.out,
+                    name=lambda s: f"step {s}")[0]
 
 
 if __name__ == "__main__":

@@ -13,15 +13,14 @@ first, each call between two device events and a synchronise behind every round:
 The times are host-enqueued calls seen by device events: at the small K they hold launch overhead, which is part of what a
 caller pays.  One JSON object per (K, topk) on stdout (and, with --out, all of them in FILE), then the table."""
 import argparse
-import dataclasses
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools import probe_common as pc  # noqa: E402
 
 P, T = 512, 0.01
 BANKS = [1000, 10000, 21841, 37888, 80000]
@@ -42,17 +41,14 @@ def _torch_route(f, bank, topk):
 def step(K, batch, reps):
     import torch
 
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
+    from mcm_amd import abi
 
-    geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-    net = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
+    net = pc.tiny_handle(P)
     g = torch.Generator(device="cuda").manual_seed(1)
     bank = torch.nn.functional.normalize(torch.randn((K, P), device="cuda", generator=g), dim=-1)
     f = torch.nn.functional.normalize(bank[torch.randint(0, K, (batch,), device="cuda", generator=g)]
                                       + 0.5 * torch.randn((batch, P), device="cuda", generator=g), dim=-1)
-    lds_ok = (P + K) * 4 <= 150 * 1024
+    lds_ok = (P + K) * 4 <= abi.DEFINES["MCM_SCORE_LDS_MAX_BYTES"]
     for topk in TOPKS:
         routes = {"stream": lambda: net.score_features(f, bank, T, "MCM", topk=topk, tail="stream"),
                   "torch": lambda: _torch_route(f, bank, topk)}
@@ -79,7 +75,7 @@ def step(K, batch, reps):
                "lds_ms": ms["lds"] / reps if lds_ok else None, "torch_ms": ms["torch"] / reps,
                "stream_tflops_fp32": 2.0 * batch * K * P / (ms["stream"] / reps) / 1e9,
                "max_abs_diff_vs_stream": diff}
-        print("PROBE " + json.dumps(res), flush=True)
+        pc.emit(res)
     net.close()
 
 
@@ -104,23 +100,11 @@ def main():
     if a.child is not None:
         step(a.child, a.batch, a.reps)
         return 0
-    results = []
-    for K in BANKS:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--batch", str(a.batch),
-               "--reps", str(a.reps), "--child", str(K)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln[6:] for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
-        for ln in lines:
-            results.append(json.loads(ln))
-            print(ln, flush=True)
-        if a.out:
-            with open(a.out, "w") as fh:
-                json.dump(results, fh, indent=1)
-        if r.returncode or len(lines) != len(TOPKS):
-            print(f"K = {K} failed (exit {r.returncode}); stopping\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", file=sys.stderr)
-            return 1
-    print(table(results))
-    return 0
+    rc, results = pc.drive(__file__, [(K,) for K in BANKS], ["--batch", a.batch, "--reps", a.reps], a.limit, a.out, len(TOPKS),
+                           lambda s: f"K = {s[0]}")
+    if not rc:
+        print(table(results))
+    return rc
 
 
 if __name__ == "__main__":

@@ -10,15 +10,14 @@ the two routes alternating in one process, both warmed up first:
              plus the norm of the basis columns), HIP events.
 One JSON object per shape on stdout (and, with --out, all of them in FILE)."""
 import argparse
-import dataclasses
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools import probe_common as pc  # noqa: E402
 
 SHAPES = [(512, 256), (1024, 512)]   # (P, R): ViT-B/16's and ViT-H/14's projection widths at the default D
 K, T, ALPHA = 1000, 0.01, 1.5
@@ -34,38 +33,18 @@ def _torch_route(f, bank):
 def step(P, R, batch, reps):
     import torch
 
-    from mcm_amd.config import geometry
-    from mcm_amd.engine import NativeCLIP
-    from mcm_amd.weights import synth_state_dict
-
-    geo = dataclasses.replace(geometry("tiny"), name=f"tiny-P{P}", proj_dim=P)
-    net = NativeCLIP(geo, synth_state_dict(geo, 0), precision="fp16", max_batch=8, max_prompt_tokens=256)
+    net = pc.tiny_handle(P)
     g = torch.Generator(device="cuda").manual_seed(1)
     prompts = torch.nn.functional.normalize(torch.randn((K, P), device="cuda", generator=g), dim=-1)
     basis = torch.linalg.qr(torch.randn((P, R), device="cuda", generator=g)).Q.T.contiguous()
     bank = torch.cat([prompts, basis]).contiguous()
     f = torch.nn.functional.normalize(prompts[torch.randint(0, K, (batch,), device="cuda", generator=g)]
                                       + 0.5 * torch.randn((batch, P), device="cuda", generator=g), dim=-1)
-    mine = net.vim_scores(f, bank, K, T=T, alpha=ALPHA)       # warm-up of both routes, and they must agree
-    ref = _torch_route(f, bank)
-    torch.cuda.synchronize()
-    agree = float((mine - ref).abs().max())
     net.profile(True)
-    net.profile_read()
-    t_ms, ev = 0.0, [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for _ in range(reps):                                     # alternating
-        net.vim_scores(f, bank, K, T=T, alpha=ALPHA)
-        ev[0].record()
-        _torch_route(f, bank)
-        ev[1].record()
-        torch.cuda.synchronize()
-        t_ms += ev[0].elapsed_time(ev[1])
-    mn = net.profile_read()["score"]
-    assert mn["launches"] == reps, mn
-    res = {"P": P, "R": R, "K": K, "N": K + R, "B": batch, "T": T, "reps": reps, "vim_ms": mn["ms"] / reps, "torch_ms": t_ms / reps,
-           "vim_over_torch": mn["ms"] / t_ms, "vim_tflops_fp32": mn["flops"] / reps / (mn["ms"] / reps) / 1e9,
-           "max_abs_diff_vs_torch": agree}
-    print("PROBE " + json.dumps(res), flush=True)
+    t = pc.agree_and_time(net, lambda: net.vim_scores(f, bank, K, T=T, alpha=ALPHA), lambda: _torch_route(f, bank), reps)
+    res = pc.emit({"P": P, "R": R, "K": K, "N": K + R, "B": batch, "T": T, "reps": reps, "vim_ms": t["ms"],
+                   "torch_ms": t["yardstick_ms"], "vim_over_torch": t["ms"] / t["yardstick_ms"],
+                   "vim_tflops_fp32": t["flops"] / t["ms"] / 1e9, "max_abs_diff_vs_torch": t["max_abs_diff"]})
     net.profile(False)
     net.close()
     return res
@@ -82,22 +61,8 @@ def main():
     if a.child is not None:
         step(a.child[0], a.child[1], a.batch, a.reps)
         return 0
-    results = []
-    for P, R in SHAPES:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--batch", str(a.batch),
-               "--reps", str(a.reps), "--child", str(P), str(R)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln[6:] for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
-        for ln in lines:
-            results.append(json.loads(ln))
-            print(ln, flush=True)
-        if a.out:
-            with open(a.out, "w") as fh:
-                json.dump(results, fh, indent=1)
-        if r.returncode or len(lines) != 1:
-            print(f"P = {P}, R = {R} failed (exit {r.returncode}); stopping\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", file=sys.stderr)
-            return 1
-    return 0
+    return pc.drive(__file__, SHAPES, ["--batch", a.batch, "--reps", a.reps], a.limit, a.out,
+                    name=lambda s: f"P = {s[0]}, R = {s[1]}")[0]
 
 
 if __name__ == "__main__":
