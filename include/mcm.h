@@ -18,7 +18,9 @@
  *   - no device allocation happens after mcm_create (workspace is sized from
  *     cfg.max_batch / cfg.max_prompt_tokens), so calls are hipGraph-capturable;
  *   - one handle is used from one host thread at a time (the reference is
- *     single-threaded: utils/detection_util.py:219).
+ *     single-threaded: utils/detection_util.py:219);
+ *   - a result depends on the call's arguments only, never on earlier calls on the handle: same arguments, same bits; the
+ *     workspace needs no initialisation between calls, and mcm_saturation_count counts the calls since its last reset only.
  */
 #ifndef MCM_H_
 #define MCM_H_

@@ -4,6 +4,8 @@ struct's fields and a constant's value.  Standard library only.
     PROTOTYPES / HARNESS_PROTOTYPES   name -> (restype, argtypes): the product entries / those under #ifdef MCM_HARNESS
     EXTENSION_PROTOTYPES              the same for the product entries that the extension headers next to mcm.h declare
                                       (include/mcm_score_stream.h); declare() binds them where they are named
+    EXTENSION_HARNESS_PROTOTYPES      ... and for the harness entries they declare under #ifdef MCM_HARNESS
+                                      (include/mcm_debug_workspace.h)
     DEFINES                           every integer `#define MCM_*` -> int
     struct_fields(name)               the ctypes `_fields_` of a struct of the header, array members included
     declare(lib, names, harness)      sets restype and argtypes on a ctypes.CDLL
@@ -22,7 +24,8 @@ import re
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mcm.h")
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double,
             **{f"{u}int{n}_t": getattr(ctypes, f"c_{u}int{n}") for u in ("", "u") for n in (8, 16, 32, 64)}}
-EXTENSION_HEADERS = ("mcm_score_stream.h",)   # read by the rules of mcm.h; each includes it and adds entries, nothing else
+# read by the rules of mcm.h; each includes it and adds entries, nothing else (under #ifdef MCM_HARNESS: harness entries)
+EXTENSION_HEADERS = ("mcm_score_stream.h", "mcm_debug_workspace.h")
 Header = collections.namedtuple("Header", "prototypes harness_prototypes defines structs")
 
 
@@ -85,13 +88,24 @@ def _read_header(path: str = HEADER_PATH) -> Header:
         return parse(f.read())
 
 
+def read_extension(path: str, taken=()) -> Header:
+    """An extension header: new entries and nothing else — product entries, and harness entries in an #ifdef MCM_HARNESS block
+    of its own.  A #define, a struct or a name in `taken` (what mcm.h and the extensions before it declare) is refused."""
+    ext = _read_header(path)
+    again = (set(ext.prototypes) | set(ext.harness_prototypes)) & set(taken) | set(ext.prototypes) & set(ext.harness_prototypes)
+    if ext.defines or ext.structs or again:
+        raise ValueError(f"include/{os.path.basename(path)}: an extension header declares new entries and nothing else"
+                         + (f" (declared before: {sorted(again)})" if again else ""))
+    return ext
+
+
 PROTOTYPES, HARNESS_PROTOTYPES, DEFINES, _STRUCTS = _read_header()
-EXTENSION_PROTOTYPES = {}
+EXTENSION_PROTOTYPES, EXTENSION_HARNESS_PROTOTYPES = {}, {}
 for _name in EXTENSION_HEADERS:
-    _ext = _read_header(os.path.join(os.path.dirname(HEADER_PATH), _name))
-    if _ext.harness_prototypes or _ext.defines or _ext.structs or set(_ext.prototypes) & set(PROTOTYPES):
-        raise ValueError(f"include/{_name}: an extension header declares new product entries and nothing else")
+    _ext = read_extension(os.path.join(os.path.dirname(HEADER_PATH), _name),
+                          {**PROTOTYPES, **HARNESS_PROTOTYPES, **EXTENSION_PROTOTYPES, **EXTENSION_HARNESS_PROTOTYPES})
     EXTENSION_PROTOTYPES.update(_ext.prototypes)
+    EXTENSION_HARNESS_PROTOTYPES.update(_ext.harness_prototypes)
 
 
 def struct_fields(name: str) -> list:
@@ -101,7 +115,7 @@ def struct_fields(name: str) -> list:
 def declare(lib, names=None, harness: bool = False):
     """Set restype and argtypes of `names` on `lib` (default: every product entry, and every harness entry with `harness`) and
     return it.  A symbol the library lacks is an error that names it; so is a name the header does not declare."""
-    table = {**PROTOTYPES, **HARNESS_PROTOTYPES, **EXTENSION_PROTOTYPES}
+    table = {**PROTOTYPES, **HARNESS_PROTOTYPES, **EXTENSION_PROTOTYPES, **EXTENSION_HARNESS_PROTOTYPES}
     if names is None:
         names = list(PROTOTYPES) + (list(HARNESS_PROTOTYPES) if harness else [])
     for name in names:

@@ -422,6 +422,17 @@ hipError_t launch_patchify(int prec, const float* pixels, void* patches, int B, 
 hipError_t launch_patchify_u8(int prec, const uint8_t* pixels, void* patches, int B, int image,
                               int patch, int kpad, const float* mean, const float* stdv,
                               hipStream_t s, bool split = false);
+// Up to four spans of device memory zeroed by ONE kernel launch: p[i] 8-byte aligned, n8[i] its length in 8-byte words.
+// Every zeroing of a capturable route goes through it, not through hipMemsetAsync.  Observed (MI355X, a GraphedScorer replay
+// on the default stream, tests/handle_history.py REGRESSIONS): the memset nodes that four hipMemsetAsync(.., 0, ..) of
+// vision_front had been captured as filled exactly their spans, but with a 16-byte periodic pattern of pointer-like words that
+// changed from replay to replay, not with zeros; eager calls and replays on a side stream zeroed.  Why the runtime does that is
+// not known.  A kernel node replays like the launches around it.
+struct ZeroSpans {
+  void* p[4];
+  size_t n8[4];
+};
+hipError_t launch_zero_spans(const ZeroSpans& z, int n, hipStream_t s);
 hipError_t launch_bank_reduce(const float* feats, int K, int T, int P, float* bank, hipStream_t s);
 hipError_t launch_text_embed(const int32_t* ids, const float* tok, const float* pos, float* x,
                              int K, int S, int D, hipStream_t s);

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "../../include/mcm_debug_workspace.h"
 #include "../../include/mcm_score_stream.h"
 #include "bank_sim.hpp"
 #include "common.hpp"
@@ -89,6 +90,7 @@ struct HandleCore {
   int64_t max_rows = 0;
   int x2_batch = 0;    // largest batch of the split-activation arm (= max_batch on fp16 handles, whose activation buffers are sized for it; 0: not fp16)
   size_t hbuf_bytes = 0;
+  size_t x_bytes = 0, ln_bytes = 0, qkv_bytes = 0, att_bytes = 0, patches_bytes = 0;  // allocated sizes (mcm_debug_workspace_fill)
   std::vector<void*> owned;       // every hipMalloc'd pointer
   // profiling
   bool prof = false;
@@ -250,9 +252,13 @@ hipError_t gemm(mcm_handle* h, hipStream_t s, int prec, int epi, const GemmArgs&
   Scope sc(h, s, MCM_KC_GEMM, 2.0 * a.M * (double)a.N * a.K, shape);  // algorithmic FLOP: the logical K, split or not
   // Row padding into the workspace: the ping-pong kernel takes problems made of whole 256-row tiles only, so a
   // dense activation GEMM whose M is not a multiple of 256 is run on M rounded up.  The extra rows exist (every
-  // activation buffer is allocated in whole 256-row tiles and zeroed once), every output row depends on its own
-  // input row only, and the pad rows' results are never read: same bits for the real rows, and batches that are not
-  // multiples of 256 images (any batch at ViT-L/14's 257 tokens but 256 k; ragged last batches) get the fast kernel.
+  // activation buffer is allocated in whole 256-row tiles), every output row depends on its own input row only, and
+  // the pad rows' results are never read: same bits for the real rows, and batches that are not multiples of 256
+  // images (any batch at ViT-L/14's 257 tokens but 256 k; ragged last batches) get the fast kernel.  What the pad rows
+  // HOLD is arbitrary: mcm_create zeroes them once, but the towers share the buffers, so a text pass pads into the
+  // 16-bit rows the last vision batch left and reads them as fp32, NaN included.  That is harmless for the outputs in
+  // every mode; only the fp16 saturation watch could see such rows, which is why vision_front zeroes them per batch.
+  // tests/test_gpu_handle_history.py holds both, over a workspace filled with NaN and with near-saturation patterns.
   const bool from_row0 = a.x == h->ln || a.x == h->att || a.x == h->hbuf;  // not a chunk that starts mid-buffer
   if (epi != EPI_PATCH && from_row0 && a.M % 256 != 0 && a.N % 256 == 0 && a.ldx == a.K && a.ldo == a.N)
     a.M = (int)padded_rows(h, a.M);
@@ -514,6 +520,7 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
   const int64_t dmax = c.v_width > c.t_width ? c.v_width : c.t_width;
   const size_t xb = (size_t)h->max_rows * dmax * sizeof(float), lnb = both(c.v_width, c.t_width),
                qkvb = both(3 * (int64_t)c.v_width, 3 * (int64_t)c.t_width), attb = both(c.v_width, c.t_width);
+  h->x_bytes = xb; h->ln_bytes = lnb; h->qkv_bytes = qkvb; h->att_bytes = attb;
   if (!rc) rc = dev_alloc(h, (void**)&h->x, xb);
   if (!rc) rc = dev_alloc(h, &h->ln, lnb);
   if (!rc) rc = dev_alloc(h, &h->qkv, qkvb);
@@ -525,7 +532,8 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
               hipMemset(h->qkv, 0, qkvb) != hipSuccess || hipMemset(h->att, 0, attb) != hipSuccess ||
               hipMemset(h->hbuf, 0, h->hbuf_bytes) != hipSuccess))
     rc = fail(h, MCM_EHIP, "hipMemset of the activation workspace");
-  if (!rc) rc = dev_alloc(h, &h->patches, std::max((size_t)c.max_batch * h->np * h->kpad * es, (size_t)h->x2_batch * h->np * h->kpad * es * 2));
+  h->patches_bytes = std::max((size_t)c.max_batch * h->np * h->kpad * es, (size_t)h->x2_batch * h->np * h->kpad * es * 2);
+  if (!rc) rc = dev_alloc(h, &h->patches, h->patches_bytes);
   if (!rc) rc = dev_alloc(h, (void**)&h->feat, (size_t)c.max_batch * c.proj_dim * sizeof(float));
   if (!rc) rc = dev_alloc(h, (void**)&h->ids_dev, (size_t)mt * sizeof(int32_t));
   if (!rc) rc = dev_alloc(h, (void**)&h->rowidx_dev, (size_t)mt * sizeof(int32_t));
@@ -728,15 +736,26 @@ int vision_front(mcm_handle* h, hipStream_t s, const void* pixels_dev, bool u8, 
   if (stage_last < 1) return MCM_OK;
   {  // Pad rows.  gemm() runs the dense activation GEMMs on whole 256-row tiles; the rows between B * ntok and the next
      // multiple of 256 are computed and never read.  The buffers they live in are shared with the fp32 text tower, so
-     // what they hold is arbitrary (fp32 bit patterns read as fp16 decode to inf / NaN, which would trip the saturation
-     // watch): a ragged batch zeroes them first, and they then only ever carry bias-only values.
+     // what they hold is arbitrary.  No output depends on them in any mode; the one thing that could is the fp16
+     // saturation watch: fp32 bit patterns read as fp16 decode to large finite values and inf, a GEMM over such rows
+     // packs out-of-range results, and the wave that packs them counts (NaN alone would not: the watch's fmaxf skips
+     // it).  So a ragged batch zeroes the pad rows of every buffer a padded GEMM READS (x, ln, att, hbuf), and they
+     // then only ever carry bias-only values; h->qkv is only ever written by a padded GEMM (attention reads the real
+     // rows) and needs none.  bf16 and fp32 handles would return the same bits and counts without the zeroing: with
+     // it removed tests/test_gpu_handle_history.py fails on fp16 handles alone, by the count, under the 0x7B fill.
     const int64_t M = (int64_t)B * h->ntok, mp = padded_rows(h, (int)M);
     if (mp > M) {
       const size_t es = (size_t)prec_esize(c.precision) * (x2 ? 2 : 1), pad = (size_t)(mp - M);
-      HIP_TRY(h, hipMemsetAsync(h->x + M * D, 0, pad * D * sizeof(float), s));
-      HIP_TRY(h, hipMemsetAsync((char*)h->ln + (size_t)M * D * es, 0, pad * D * es, s));
-      HIP_TRY(h, hipMemsetAsync((char*)h->att + (size_t)M * D * es, 0, pad * D * es, s));
-      HIP_TRY(h, hipMemsetAsync((char*)h->hbuf + (size_t)M * c.v_mlp * es, 0, pad * c.v_mlp * es, s));
+      // One kernel, not four hipMemsetAsync (ZeroSpans, common.hpp).  Observed with the memsets, on a fresh fp16 `tiny`
+      // handle, whose pad rows mcm_create zeroed and no route writes: behind a GraphedScorer replay on the default stream
+      // the pad rows of h->att, then of h->ln, held a non-zero pattern (|v| up to 55 136 as fp16) — the replayed memset
+      // nodes had written it —, the next replay's fc1 packed rows 51 ... 255 of h->hbuf up to 65 056, and the count was 7
+      // to 112 for a fresh handle's 0, the outputs untouched.  Rows and buffers are read back from the device; that the
+      // runtime's memset nodes are at fault, and not this code, is supposed from the kernel in their place counting 0.
+      const ZeroSpans z{{h->x + M * D, (char*)h->ln + (size_t)M * D * es, (char*)h->att + (size_t)M * D * es,
+                         (char*)h->hbuf + (size_t)M * c.v_mlp * es},
+                        {pad * D * sizeof(float) / 8, pad * D * es / 8, pad * D * es / 8, pad * c.v_mlp * es / 8}};
+      HIP_TRY(h, launch_zero_spans(z, 4, s));
     }
   }
   // the CLS row of every image (class_embedding + position_embedding[0], HF :212-217) is produced inside the
@@ -1022,16 +1041,17 @@ int local_pass(mcm_handle* h, hipStream_t s, int32_t B, float* local_dev) {
   const Tower& t = h->vis;
   const int D = c.v_width, P = c.proj_dim, M = B * h->ntok, prec = t.prec, es = prec_esize(prec);
   const LayerW& w = t.L[t.layers - 1];
-  HIP_TRY(h, hipMemsetAsync(h->x, 0, (size_t)M * D * sizeof(float), s));
+  HIP_TRY(h, launch_zero_spans(ZeroSpans{{h->x}, {(size_t)M * D * sizeof(float) / 8}}, 1, s));  // (D is even: whole words)
   GemmArgs o{};
   o.x = (const char*)h->qkv + (size_t)2 * D * es; o.w = w.wo; o.bias = w.bo; o.resid = h->x;
   o.M = M; o.N = D; o.K = D; o.ldx = 3 * D; o.ldo = D; o.ksplit = t.split ? 1 : 0;
   HIP_TRY(h, gemm(h, s, prec, EPI_RESID, o));
   HIP_TRY(h, lnorm(h, s, prec, h->x, W(h, "vision_model.post_layernorm.weight"), W(h, "vision_model.post_layernorm.bias"),
                    h->ln, M, D, false));
-  // (gemm() runs this one on whole 256-row tiles where the workspace has them: the pad rows of h->ln are zero or hold
-  // LayerNorm outputs of an earlier batch, their products land behind row M of h->hbuf and are never read)
-  HIP_TRY(h, hipMemsetAsync(h->hbuf, 0, (size_t)padded_rows(h, M) * P * sizeof(float), s));
+  // (gemm() runs this one on whole 256-row tiles where the workspace has them: the pad rows of h->ln are zero —
+  // vision_front zeroed them for this batch and nothing behind it writes past row M of h->ln —, their products land
+  // behind row M of h->hbuf and are never read)
+  HIP_TRY(h, launch_zero_spans(ZeroSpans{{h->hbuf}, {(size_t)padded_rows(h, M) * P * sizeof(float) / 8}}, 1, s));  // (256 | rows)
   GemmArgs p{};
   p.x = h->ln; p.w = h->wproj; p.bias = nullptr; p.resid = (float*)h->hbuf;
   p.M = M; p.N = P; p.K = D; p.ldx = D; p.ldo = P; p.ksplit = t.split ? 1 : 0;
@@ -1769,6 +1789,30 @@ int mcm_debug_op_text_embed_ctx(mcm_handle* h, const int32_t* ids_host, const in
   (void)hipFree(words_dev);
   if (refused) return fail(h, MCM_EINVAL, "launch_text_embed_ctx refused the call (D % 4 == 0, ctx 16-byte aligned)");
   HIP_TRY(h, e);
+  return MCM_OK;
+}
+
+// The activation workspace and the feature scratch filled with one byte value over their full allocated sizes, pad rows
+// included (include/mcm_debug_workspace.h): data only, no ring, counter, weight, index buffer or fault word
+int mcm_debug_workspace_fill(mcm_handle* h, int32_t byte, void* stream) {
+  if (!h) return MCM_EINVAL;
+  if (byte < 0 || byte > 255) return fail(h, MCM_EINVAL, "byte 0 ... 255");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t feat_bytes = (size_t)h->cfg.max_batch * h->cfg.proj_dim * sizeof(float);
+  const std::pair<void*, size_t> bufs[] = {{h->x, h->x_bytes},     {h->ln, h->ln_bytes},           {h->qkv, h->qkv_bytes},
+                                           {h->att, h->att_bytes}, {h->hbuf, h->hbuf_bytes},       {h->patches, h->patches_bytes},
+                                           {h->feat, feat_bytes}};
+  for (const auto& b : bufs)
+    if (b.first && b.second) HIP_TRY(h, hipMemsetAsync(b.first, byte, b.second, s));
+  return MCM_OK;
+}
+
+// The walk direction the next launch of the handle's towers takes (next_dir): read into *parity_out (may be NULL), then set to
+// `set` where that is 0 or 1 (-1: left as it is).  Host state only.
+int mcm_debug_walk_parity(mcm_handle* h, int32_t set, int32_t* parity_out) {
+  if (!h || set < -1 || set > 1) return MCM_EINVAL;
+  if (parity_out) *parity_out = h->flip ? 1 : 0;
+  if (set >= 0) h->flip = set != 0;
   return MCM_OK;
 }
 

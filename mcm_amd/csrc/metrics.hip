@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void hist_kernel(const float* __restrict__ x, 
 hipError_t launch_histogram(const float* x, long n, const float* edges, int nb, unsigned long long* counts,
                             hipStream_t s) {
   if ((!x && n) || !edges || !counts || n < 0 || nb <= 0 || nb > HB_MAX) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(counts, 0, (size_t)nb * sizeof(unsigned long long), s);
+  hipError_t e = launch_zero_spans(ZeroSpans{{counts}, {(size_t)nb}}, 1, s);  // (not hipMemsetAsync: ZeroSpans, common.hpp)
   if (e != hipSuccess || n == 0) return e;
   const long blocks = (n + 255) / 256;
   hipLaunchKernelGGL(hist_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, x, n, edges, nb,

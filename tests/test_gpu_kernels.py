@@ -362,7 +362,7 @@ def test_linear_l14_shapes_pingpong_bitwise(tiny_net, harness_net, N, K, epi):
         ref = run(0)
         assert torch.isfinite(ref.float()).all()
         for variant in (-1, 5, 9):
-            for _ in range(2):  # mcm_op_linear alternates the walk direction per launch: both get exercised
+            for _ in range(2):  # twice: the same bits on a repeat (mcm_op_linear always walks forward; the towers alternate)
                 got = run(variant)
                 view = torch.int32 if epi == 2 else torch.int16
                 assert torch.equal(got.view(view), ref.view(view)), f"variant {variant}"
