@@ -140,7 +140,23 @@ typedef struct mcm_config {
 int mcm_abi_version(void);
 
 /* Replaces CLIPModel.__init__ + .cuda() (utils/train_eval_util.py:23-24): allocates the
- * parameter store and the activation workspace on cfg->device. */
+ * parameter store and the activation workspace on cfg->device.
+ *
+ * The geometries it accepts — every one of these is a model the kernels compute, held to the CPU oracle and to fp64 operator
+ * budgets at points away from the shipped checkpoints (tests/geometry_envelope.py, tests/test_gpu_geometry_envelope.py);
+ * anything else is MCM_EINVAL with the rule in mcm_last_error(NULL), before any device memory is touched:
+ *   v_width        64 * v_heads with v_heads = 1 ... 20, or 80 * v_heads with 80 * v_heads a multiple of 64 (4, 8, 12, 16
+ *                  heads); 320 is both 5 heads of 64 and 4 heads of 80, and v_heads says which
+ *   t_width        64 * t_heads, at most 1024 (the text tower has no 80-wide heads)
+ *   v_mlp, t_mlp   any multiple of 64
+ *   proj_dim       any multiple of 4 up to 1024
+ *   patch_size     any divisor of image_size that leaves at most 1025 vision tokens ((image_size / patch_size)^2 + 1);
+ *                  image_size == patch_size is the 2-token tower
+ *   v_layers, t_layers   at least 1 (a one-layer tower is its first and its last layer at once; there is no zero-layer tower)
+ *   max_positions  1 ... 306: the text tower's causal fp32 attention keeps K, V and the logits of a head in LDS, and 306 tokens
+ *                  are the longest prompt that fits (Long-CLIP's 248 does); at most max_prompt_tokens
+ *   vocab_size     any; v_hidden_act, t_hidden_act: MCM_ACT_QUICK_GELU or MCM_ACT_GELU
+ * A prompt longer than max_positions is MCM_ERANGE from mcm_encode_text*, as HF raises. */
 int mcm_create(const mcm_config* cfg, mcm_handle** out);
 void mcm_destroy(mcm_handle* h);
 const char* mcm_last_error(const mcm_handle* h); /* h may be NULL: last create error */

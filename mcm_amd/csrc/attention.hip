@@ -1766,6 +1766,10 @@ void attention_set_variant(int v) { g_attn_variant = v; }
 void attention_set_spin_budget(unsigned int polls) { g_ps_spin_budget = polls; }
 #endif
 
+// attn_f32_kernel's LDS: Ks [L][65], Vs [L][64], qs [4][64], ps [4][L] floats, against the cap launch_lds holds it to
+constexpr int ATTN_F32_LDS_CAP = 160 * 1024;
+constexpr int attn_f32_lds_bytes(int L) { return (L * 65 + L * 64 + 4 * 64 + 4 * L) * (int)sizeof(float); }
+
 hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads, int head_dim,
                             bool causal, int qrows, hipStream_t s, bool reverse, int hm, bool split, unsigned int* fault) {
   if (nseq <= 0 || L <= 0 || heads <= 0) return hipErrorInvalidValue;
@@ -1834,8 +1838,14 @@ hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int 
     MCM_F32A(2, 4); MCM_F32A(4, 4); MCM_F32A(8, 4); MCM_F32A(13, 8); MCM_F32A(18, 8);
 #undef MCM_F32A
   }
-  const int lds = (L * 65 + L * 64 + 4 * 64 + 4 * L) * (int)sizeof(float);
+  const int lds = attn_f32_lds_bytes(L);
   const dim3 grid(nseq * heads), block(256);
-  if (causal) return launch_lds<attn_f32_kernel<true>, 160 * 1024>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
-  return launch_lds<attn_f32_kernel<false>, 160 * 1024>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
+  if (causal) return launch_lds<attn_f32_kernel<true>, ATTN_F32_LDS_CAP>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
+  return launch_lds<attn_f32_kernel<false>, ATTN_F32_LDS_CAP>(grid, block, lds, s, (const float*)qkv, (float*)out, L, heads, qrows);
+}
+
+int attention_causal_f32_max_len() {
+  int L = 1;
+  while (attn_f32_lds_bytes(L + 1) <= ATTN_F32_LDS_CAP) ++L;
+  return L;
 }

@@ -415,6 +415,9 @@ hipError_t launch_layernorm_pre(int prec, float* x, const float* g0, const float
 hipError_t launch_attention(int prec, const void* qkv, void* out, int nseq, int L, int heads, int head_dim,
                             bool causal, int qrows, hipStream_t s, bool reverse = false, int hm = 0, bool split = false,
                             unsigned int* fault = nullptr);   // fault: the handle's host-mapped kernel-fault word (attn_ps_kernel)
+// the longest sequence the causal fp32 form (the text tower's) launches: K, V and the logits of a head in LDS (mcm_create
+// refuses a max_positions past it)
+int attention_causal_f32_max_len();
 
 // split: the patch matrix as a split image [B*np, 2 kpad] (fp16; GemmArgs::xsplit)
 hipError_t launch_patchify(int prec, const float* pixels, void* patches, int B, int image,

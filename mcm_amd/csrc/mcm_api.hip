@@ -452,6 +452,14 @@ int mcm_create(const mcm_config* cfg, mcm_handle** out) {
   if (c.max_batch <= 0 || c.max_prompt_tokens <= 0 || c.max_positions <= 0 ||
       c.max_prompt_tokens < c.max_positions)
     return fail(nullptr, MCM_EINVAL, "bad workspace bounds");
+  // a tower without layers is not a CLIP tower: the first layer's LayerNorm is fused into the front of each tower, and the last
+  // one is the CLS-only / pooled-row form, so there is no zero-layer path to fall back to
+  if (c.v_layers < 1 || c.t_layers < 1) return fail(nullptr, MCM_EINVAL, "v_layers and t_layers must be at least 1");
+  // the text tower's attention is the causal fp32 kernel, which keeps K, V and the logits of a head in LDS: a prompt of
+  // max_positions tokens has to launch (attention.hip attn_f32_kernel)
+  if (c.max_positions > attention_causal_f32_max_len())
+    return fail(nullptr, MCM_EINVAL, "max_positions exceeds " + std::to_string(attention_causal_f32_max_len()) +
+                                         ", the longest prompt the causal fp32 attention launches");
   {
     const int g = c.image_size / c.patch_size;
     // attention's ceiling (attention.hip LONG_MAX_L): 288 tokens keep K and V of a head in LDS, up to 1025 stream them

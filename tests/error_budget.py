@@ -645,8 +645,11 @@ def pool_project_budget(x, g, b, proj, normalize: bool, eps=1e-5):
                   here once D > 640: a path then has up to 16 fmaf roundings and 6 butterfly adds, 22 > 16.  The kernel-order
                   emulation stays below 0.14 of the whole budget at every D (test_pool_project_emulation_within_budget);
       normalise   the squares of a wave's outputs (every 16th p) summed by its lane 0 one after another (ceil(P / 16) terms),
-                  then the 16 partials: l2_normalise_budget with n_add = ceil(P / 16) + 16."""
-    y, dy = layernorm_budget(x, g, b, "fp32", eps, depth=6 + POOL_WAVES)
+                  then the 16 partials: l2_normalise_budget with n_add = ceil(P / 16) + 16.
+    1024 < D <= 1280 (pool_project_kernel<WIDE>): a thread adds its two elements, t and t + 1024, before the wave_sum: one more
+    level of the LayerNorm's tree; the rest as above."""
+    wide = int(np.shape(x)[1] > 1024)
+    y, dy = layernorm_budget(x, g, b, "fp32", eps, depth=wide + 6 + POOL_WAVES)
     w64 = np.asarray(proj, np.float64)
     o = y @ w64.T
     do = dy @ np.abs(w64).T + C_ACC * U32 * (np.abs(y) @ np.abs(w64).T)

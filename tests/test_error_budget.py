@@ -214,26 +214,33 @@ def _ln_rows(D, seed):
     return x, g, b
 
 
-def _ln_emulate(x, g, b, out, single_pass=False, eps=1e-5):
+def _ln_emulate(x, g, b, out, single_pass=False, eps=1e-5, no_column_test=False):
     """ln_row.hpp in fp32: lane partial sums of the row (columns (i * 64 + lane) * 4 + 0..3), the wave butterfly, mean,
-    centred sum of squares the same way, rstd = 1 / sqrtf(var / D + eps), fma(c * rstd, g, b)."""
+    centred sum of squares the same way, rstd = 1 / sqrtf(var / D + eps), fma(c * rstd, g, b).
+    no_column_test: ln_has without its "column < D" test: the lanes of the last, partial vector slot whose columns lie past
+    the row add what is there — the start of the next row (zeros after the last one) — into the row's sums."""
     M, D = x.shape
     eps = F32(eps)
+    xs = _f32(x)
+    W = D                   # columns a lane's "do I hold this vector" test lets through
+    if no_column_test:      # every slot whole: each row followed by what lies behind it in memory
+        W = (D + 255) // 256 * 256
+        flat = np.concatenate([xs.ravel(), np.zeros(W, F32)])
+        xs = np.stack([flat[r * D:r * D + W] for r in range(M)])
 
-    def wave_total(vals):  # vals [M, D] fp32 -> the kernel's sum order
+    def wave_total(vals):  # vals [M, W] fp32 -> the kernel's sum order
         nv = (D + 255) // 256
         lane = np.zeros((M, 64), F32)
         for i in range(nv):
             for ln in range(64):
                 d = (i * 64 + ln) * 4
-                if d < D:
+                if d < W:
                     v = vals[:, d:d + 4]
                     lane[:, ln] = lane[:, ln] + _f32((v[:, 0] + v[:, 1]) + (v[:, 2] + v[:, 3]))
         for o in (32, 16, 8, 4, 2, 1):
             lane = _f32(lane + lane[:, np.arange(64) ^ o])
         return lane[:, :1]
 
-    xs = _f32(x)
     mean = _f32(wave_total(xs) / F32(D))
     if single_pass:
         msq = _f32(wave_total(_f32(xs * xs)) / F32(D))
@@ -242,12 +249,15 @@ def _ln_emulate(x, g, b, out, single_pass=False, eps=1e-5):
     else:
         c = _f32(xs - mean)
         var = _f32(wave_total(_f32(c * c)) / F32(D))
+    c = c[:, :D]
     rstd = _f32(F32(1) / np.sqrt(_f32(var + eps)))
     y = _f32(_f32(c * rstd).astype(np.float64) * g + b)
     return y if out == "fp32" else eb.round_to(y, out)
 
 
-@pytest.mark.parametrize("D", [128, 768, 1024])
+# 192 ... 1216: widths inside mcm_create's envelope with a partial 256-column vector slot, alone (192) or behind whole ones
+# (320, 832; 1088 and 1216: the five-vector kernels of layernorm.hip with a partial fifth vector)
+@pytest.mark.parametrize("D", [128, 768, 1024, 192, 320, 832, 1088, 1216])
 @pytest.mark.parametrize("out", ["bf16", "fp16", "fp32"])
 def test_layernorm_emulation_within_budget_and_single_pass_breaks_it(D, out):
     x, g, b = _ln_rows(D, D)
@@ -257,6 +267,19 @@ def test_layernorm_emulation_within_budget_and_single_pass_breaks_it(D, out):
     with np.errstate(invalid="ignore"):
         r_bad, i = eb.worst(_ln_emulate(x, g, b, out, single_pass=True), ref, bud)
     print(f"layernorm D={D} {out}: correct {r:.3g}, single-pass {r_bad:.3g} (row {i // D})")
+    assert r_bad > 1.0
+
+
+@pytest.mark.parametrize("D", [192, 320, 832, 1088, 1216])
+@pytest.mark.parametrize("out", ["bf16", "fp16", "fp32"])
+def test_layernorm_partial_vector_without_its_column_test_breaks_the_budget(D, out):
+    """A partial last vector slot whose lanes skip the "column < D" test (ln_row.hpp ln_has) takes the next row's first
+    columns into the mean and the variance: far outside the budget at every such width, on the GPU test's own rows."""
+    x, g, b = _ln_rows(D, D)
+    ref, bud = eb.layernorm_budget(x, g, b, out)
+    with np.errstate(invalid="ignore"):
+        r_bad, _ = eb.worst(_ln_emulate(x, g, b, out, no_column_test=True), ref, bud)
+    print(f"layernorm D={D} {out}: no column test {r_bad:.3g}")
     assert r_bad > 1.0
 
 
@@ -975,18 +998,27 @@ def _pool_emulate(x, g, b, proj, normalize, mutation=None, eps=1e-5):
     n, D = x.shape
     P = proj.shape[0]
     eps = F32(eps)
-    xp = np.zeros((n, 1024), F32)
+    wide = D > 1024       # pool_project_kernel<WIDE>: thread t holds x[t] and x[t + 1024]
+    W = 2048 if wide else 1024
+    xp = np.zeros((n, W), F32)
     xp[:, :D] = x
 
     def block_total(v):   # [n, 1024] -> [n]
         return _seq_sum(_butterfly(v.reshape(n, 16, 64))[:, :, 0])
 
-    mean = _f32(block_total(xp) / F32(D))[:, None]
-    c = np.where(np.arange(1024) < D, _f32(xp - mean), F32(0))
+    def thread_sum(v):    # what a thread hands to wave_sum: its element, or (WIDE) xv + xw
+        return _f32(v[:, :1024] + v[:, 1024:]) if wide else v
+
+    def thread_sq(v):     # c * c, or (WIDE) fmaf(cw, cw, c * c)
+        sq = _f32(v[:, :1024] * v[:, :1024])
+        return _f32(v[:, 1024:].astype(np.float64) ** 2 + sq) if wide else sq
+
+    mean = _f32(block_total(thread_sum(xp)) / F32(D))[:, None]
+    c = np.where(np.arange(W) < D, _f32(xp - mean), F32(0))
     if mutation == "single_pass":
-        var = _f32(_f32(block_total(_f32(xp * xp)) / F32(D)) - _f32(mean[:, 0] * mean[:, 0]))
+        var = _f32(_f32(block_total(thread_sq(xp)) / F32(D)) - _f32(mean[:, 0] * mean[:, 0]))
     else:
-        var = _f32(block_total(_f32(c * c)) / F32(D))
+        var = _f32(block_total(thread_sq(c)) / F32(D))
     with np.errstate(invalid="ignore", divide="ignore"):
         if mutation == "eps_outside":
             rstd = _f32(F32(1) / _f32(np.sqrt(var) + eps))
@@ -1017,6 +1049,11 @@ def _pool_emulate(x, g, b, proj, normalize, mutation=None, eps=1e-5):
 
 
 POOL_CASES = [(64, 1), (320, 17), (512, 64), (768, 512), (1020, 768), (1024, 1024)]
+# widths and proj_dims inside mcm_create's envelope and off the checkpoints': 64 x an odd number, whole 256-column rounds of
+# the projection plus a partial one, two elements per thread with the second round partial (1088, 1216); P below the 16 waves
+# of the workgroup, and no multiple of 16
+POOL_CASES += [(192, 4), (192, 260), (320, 100), (320, 1020), (832, 260), (832, 4), (1088, 1020), (1088, 4), (1216, 100),
+               (1216, 260)]
 
 
 @pytest.mark.parametrize("D,P", POOL_CASES)
@@ -1035,7 +1072,7 @@ def test_pool_project_emulation_within_budget(D, P):
 def test_pool_project_mutations_break_the_budget(mutation):
     """E[x^2] - mean^2 (shows on the rows of mean 1e3), eps added to the standard deviation instead of the variance, the
     projection fed a bf16-rounded y, the norm taken from fp16-rounded outputs."""
-    for D, P in ((512, 64), (768, 512), (1024, 768)):
+    for D, P in ((512, 64), (768, 512), (1024, 768), (1088, 260)):
         x = ends._pool_rows(25, D, D)
         g, b, proj = ends._pool_params(D, P, D + P)
         ref, bud = eb.pool_project_budget(x, g, b, proj, True)

@@ -42,9 +42,12 @@ _check = functools.partial(gs.check_budget, finite_budget=True)
 # ---- handles -----------------------------------------------------------------------------------------------------------
 def _geo(name):
     """The named geometry; the full checkpoints with one encoder layer per tower (the front and the pooling kernels do not
-    depend on the layers behind them, and a handle is then created in a fraction of the time)."""
-    from mcm_amd.config import CHECKPOINTS, geometry
+    depend on the layers behind them, and a handle is then created in a fraction of the time).  A ClipGeometry is taken as
+    it is (tests/test_gpu_geometry_envelope.py)."""
+    from mcm_amd.config import CHECKPOINTS, ClipGeometry, geometry
 
+    if isinstance(name, ClipGeometry):
+        return name
     geo = geometry(name)
     return dataclasses.replace(geo, name=name + "-1L", v_layers=1, t_layers=1) if name in CHECKPOINTS else geo
 
