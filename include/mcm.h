@@ -13,14 +13,32 @@
  *   - every function returns 0 on success or a negative MCM_E* code and never throws;
  *     mcm_last_error(h) returns a human-readable message for the last failure;
  *   - `*_dev` pointers are device (HBM) addresses, `*_host` pointers are host addresses;
- *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); all compute
- *     entry points are asynchronous on it;
- *   - no device allocation happens after mcm_create (workspace is sized from
- *     cfg.max_batch / cfg.max_prompt_tokens), so calls are hipGraph-capturable;
+ *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); what an entry promises about it is its class
+ *     in the "Stream contract" below, which every entry with a `stream` names in the last sentence of its comment;
+ *   - the activation workspace is allocated by mcm_create (sized from cfg.max_batch / cfg.max_prompt_tokens); the
+ *     entries that allocate later are the host_staged ingest entries, on a first or a growing call;
  *   - one handle is used from one host thread at a time (the reference is
  *     single-threaded: utils/detection_util.py:219);
  *   - a result depends on the call's arguments only, never on earlier calls on the handle: same arguments, same bits; the
  *     workspace needs no initialisation between calls, and mcm_saturation_count counts the calls since its last reset only.
+ *
+ * Stream contract — every entry with a `stream` parameter is in one of three classes (the table, with the line of code that
+ * decides each entry: tests/stream_contract.py; held by tests/test_gpu_stream_contract.py):
+ *   replayable     asynchronous on `stream`; no allocation, no host synchronisation, and no host array read at call time.
+ *                  The call may be captured into a hipGraph and replayed: a replay computes from what the buffers hold then
+ *                  and writes the bits the eager call writes; scalars and pointers are baked into the graph.  Make one call
+ *                  with the same arguments outside the capture first (the first launch of a kernel with dynamic LDS raises
+ *                  its limit), and keep per-kernel timing (mcm_profile_enable) off while capturing.
+ *                  Every entry with a `stream` that is not named under the two classes below.
+ *   host_staged    correct on any stream and asynchronous or nearly so, but NOT capturable: the entry reads host arrays at
+ *                  call time (they may be reused as soon as it returns), and it waits on an event of its staging ring, or
+ *                  drains `stream` before it rewrites its pinned staging buffer, or allocates on a first or a growing call:
+ *                  mcm_encode_text, mcm_encode_text_ex, mcm_encode_text_ctx, mcm_resize_crop_u8, mcm_jpeg_reconstruct.
+ *   synchronising  returns host results and drains `stream` before it returns: mcm_measures, mcm_saturation_count.
+ * ONE STREAM PER HANDLE AT A TIME: the activation workspace, the feature scratch and the pinned staging buffers are the
+ * handle's, one of each.  Calls on one handle must be ordered — issued on one stream, or on several ordered by events —;
+ * two calls on one handle on two unordered streams race on those buffers (the text path drains only the current call's
+ * stream before it rewrites its staging buffer).  Two handles are independent.
  */
 #ifndef MCM_H_
 #define MCM_H_
@@ -182,7 +200,9 @@ int mcm_weights_operand_exact(mcm_handle* h, uint64_t* inexact_host, int32_t* sp
  * ids_host: int32 [K,S] row-major, each row BOS … EOS pad…; the pooled row is the
  * first EOS (= argmax id, modeling_clip.py:561-581).  attention_mask is not needed:
  * the mask is causal and pooling reads the first EOS.
- * out_dev: fp32 [K, proj_dim], L2-normalised rows. */
+ * out_dev: fp32 [K, proj_dim], L2-normalised rows.
+ * The prompts run in passes of max_prompt_tokens / S; before each pass, the first included, the call drains `stream` and
+ * stages the pass's ids through the handle's pinned buffer.  Stream contract: host_staged. */
 int mcm_encode_text(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S,
                     float* out_dev, void* stream);
 
@@ -190,18 +210,20 @@ int mcm_encode_text(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S
  * (utils/detection_util.py:225-226; modeling_clip.py:719-753).
  * pixels_dev: fp32 NCHW [B,3,image_size,image_size] contiguous, already normalised by
  * the preprocess of utils/train_eval_util.py:27-33.
- * out_dev: fp32 [B, proj_dim], L2-normalised rows. */
+ * out_dev: fp32 [B, proj_dim], L2-normalised rows.  Stream contract: replayable. */
 int mcm_encode_image(mcm_handle* h, const float* pixels_dev, int32_t B, float* out_dev,
                      void* stream);
 
 /* The two calls above with the reference's `/= norm` step optional: normalize == 0 returns exactly what
  * HF `get_image_features` / `get_text_features` return (modeling_clip.py:751,713 — the projection
  * output), which is what unmodified reference code expects from `net` (utils/detection_util.py:158,
- * 187,225,229) before it normalises the rows itself.  pixel_format selects the ingest layout. */
+ * 187,225,229) before it normalises the rows itself.  pixel_format selects the ingest layout.
+ * mcm_encode_image_ex — Stream contract: replayable. */
 #define MCM_PIXELS_F32_NCHW 0 /* fp32 [B,3,S,S], already normalised (mcm_encode_image)            */
 #define MCM_PIXELS_U8_NHWC 1  /* uint8 [B,S,S,3]; ToTensor + Normalize fused (mcm_encode_image_u8) */
 int mcm_encode_image_ex(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B,
                         int32_t normalize, float* out_dev, void* stream);
+/* mcm_encode_text with `normalize` (above); staged as mcm_encode_text is.  Stream contract: host_staged. */
 int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_t S, int32_t normalize,
                        float* out_dev, void* stream);
 
@@ -219,21 +241,23 @@ int mcm_encode_text_ex(mcm_handle* h, const int32_t* ids_host, int32_t K, int32_
  * stream has passed the call.  Nothing is allocated: the slot map travels in the id words a pass uploads anyway.
  * out_dev: fp32 [K, proj_dim]; normalize as mcm_encode_text_ex.
  * MCM_EINVAL, with nothing launched: a NULL ids_host / slot_host / ctx_dev / out_dev; K, S or n_ctx < 1; n_sets other than 1 or K;
- * a slot outside -1 ... n_ctx - 1; an id outside the vocabulary; ctx_dev not 16-byte aligned.  MCM_ERANGE: S > max_positions. */
+ * a slot outside -1 ... n_ctx - 1; an id outside the vocabulary; ctx_dev not 16-byte aligned.  MCM_ERANGE: S > max_positions.
+ * Staged as mcm_encode_text is (ids and slots are read on the host, `stream` is drained before every pass).
+ * Stream contract: host_staged. */
 int mcm_encode_text_ctx(mcm_handle* h, const int32_t* ids_host /* [K,S] */, const int32_t* slot_host /* [K,S] */,
                         int32_t K, int32_t S, const float* ctx_dev /* [n_sets, n_ctx, t_width] fp32 */,
                         int32_t n_ctx, int32_t n_sets, int32_t normalize, float* out_dev, void* stream);
 
 /* Replaces the scoring tail utils/detection_util.py:232-248 on already-normalised
  * features: sim = img @ text.T, softmax(sim/T), reduction `kind` → scores_dev fp32 [B].
- * Never materialises [B,K]. */
+ * Never materialises [B,K].  Stream contract: replayable. */
 int mcm_score_features(mcm_handle* h, const float* img_feat_dev, int32_t B,
                        const float* text_feat_dev, int32_t K, float T, int32_t kind,
                        float* scores_dev, void* stream);
 
 /* One batch of the whole hot loop body utils/detection_util.py:223-248:
  * mcm_encode_image + mcm_score_features, text bank pre-encoded (hoisted out of the
- * loop; the reference re-encodes it every batch with identical results). */
+ * loop; the reference re-encodes it every batch with identical results).  Stream contract: replayable. */
 int mcm_score(mcm_handle* h, const float* pixels_dev, int32_t B, const float* text_feat_dev,
               int32_t K, float T, int32_t kind, float* scores_dev, void* stream);
 
@@ -257,7 +281,7 @@ int mcm_score(mcm_handle* h, const float* pixels_dev, int32_t B, const float* te
  * mcm_score_topk is one batch of the hot loop body with it (mcm_score / mcm_score_u8 / mcm_score_x2 in one entry):
  * pixel_format is MCM_PIXELS_*; x2 != 0 runs the split-activation arm under the rules of mcm_score_x2 (fp16 handle with
  * the workspace, B <= the arm's largest batch — otherwise MCM_EINVAL / MCM_ERANGE), x2 == 0 the handle's own arm through
- * the encode calls of mcm_score / mcm_score_u8.  Asynchronous on `stream`, no allocation, graph-capturable. */
+ * the encode calls of mcm_score / mcm_score_u8.  Both entries — Stream contract: replayable. */
 #define MCM_TOPK_MAX 8
 #define MCM_SCORE_LDS_MAX_BYTES 153600 /* 150 KiB: the LDS of the tail that keeps (proj_dim + K) floats per image */
 int mcm_score_features_topk(mcm_handle* h, const float* img_feat_dev, int32_t B, const float* text_feat_dev,
@@ -270,7 +294,7 @@ int mcm_score_topk(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, 
 /* uint8 ingest: pixels_dev is uint8 NHWC [B,image_size,image_size,3] (what a
  * JPEG decoder + resize/crop produces); ToTensor (/255) and Normalize with the CLIP mean/std of
  * utils/train_eval_util.py:27-33 are fused into the patch gather.  Same results as
- * mcm_encode_image / mcm_score on the equivalent fp32 NCHW tensor. */
+ * mcm_encode_image / mcm_score on the equivalent fp32 NCHW tensor.  Both entries — Stream contract: replayable. */
 int mcm_encode_image_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, float* out_dev,
                         void* stream);
 int mcm_score_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, const float* text_feat_dev,
@@ -286,7 +310,7 @@ int mcm_score_u8(mcm_handle* h, const uint8_t* pixels_dev, int32_t B, const floa
  * (reference utils/detection_util.py:66-106: FPR95 is a count at one threshold).  No second handle, no extra weights:
  * the split rows (twice the width) live in the same activation buffers, which mcm_create sizes for cfg.x2_max_batch images
  * of them: B <= mcm_x2_max_batch(h) (0 = this handle is not fp16, or was created without the workspace).  pixel_format: MCM_PIXELS_*.
- * Asynchronous on `stream`, no allocation, like mcm_score. */
+ * mcm_encode_image_x2 and mcm_score_x2 — Stream contract: replayable. */
 int mcm_x2_max_batch(const mcm_handle* h);
 int mcm_encode_image_x2(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B, int32_t normalize,
                         float* out_dev, void* stream);
@@ -300,8 +324,10 @@ int mcm_score_x2(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, in
  * src_dev_ptrs / heights / widths are HOST arrays of length B: device pointers to [H_i, W_i, 3]
  * uint8 RGB images and their sizes.  dst_dev [B, S, S, 3] uint8 is the layout mcm_score_u8 and
  * mcm_encode_image_u8 take.  MCM_ERANGE: B > max_batch, or a scale factor above 31 (more filter
- * taps than the kernel holds).  Asynchronous on `stream` (the geometry is staged through a small ring of pinned
- * buffers; the call never drains the stream), so a batch can be resized while the previous one is being scored. */
+ * taps than the kernel holds).  Asynchronous on `stream`: the geometry is staged through a ring of four pinned buffers, and
+ * a call waits only for the copy out of its slot, four calls ago (it never drains the stream), so a batch can be resized
+ * while the previous one is being scored.  The host arrays are read at call time; the first call on a handle allocates the
+ * kernel's coefficient tables (one synchronous device allocation).  Stream contract: host_staged. */
 int mcm_resize_crop_u8(mcm_handle* h, const uint8_t* const* src_dev_ptrs, const int32_t* heights,
                        const int32_t* widths, int32_t B, uint8_t* dst_dev, void* stream);
 
@@ -338,7 +364,11 @@ int mcm_jpeg_entropy_decode(const char* const* paths, int32_t n, void* dst, int6
  * (jpeg_idct_islow), fancy chroma upsampling and YCbCr -> RGB: uint8 [height_i, width_i, 3] at rgb_dev + rgb_offsets[i] —
  * byte for byte what Pillow's Image.open(path).convert("RGB") returns (the reference's loader decodes with it).  meta / quant /
  * rgb_offsets are HOST arrays of length n; images whose status is not 0 are skipped (the caller decodes those with its
- * fallback and writes their pixels itself).  Asynchronous on `stream`; the output is what mcm_resize_crop_u8 takes. */
+ * fallback and writes their pixels itself).  Asynchronous on `stream` in the steady state; the output is what
+ * mcm_resize_crop_u8 takes.  The host arrays are read at call time into a ring of four pinned buffers (a call waits for the
+ * copy out of its slot, four calls ago); the first call on a handle allocates the ring, and a batch whose sample planes
+ * exceed the handle's buffer grows it: `stream` is drained, the buffer freed and allocated again.
+ * Stream contract: host_staged. */
 int mcm_jpeg_reconstruct(mcm_handle* h, const void* coef_dev, const mcm_jpeg_image* meta, const uint16_t* quant, int32_t n,
                          uint8_t* rgb_dev, const int64_t* rgb_offsets, void* stream);
 
@@ -346,7 +376,7 @@ int mcm_jpeg_reconstruct(mcm_handle* h, const void* coef_dev, const mcm_jpeg_ima
  * features [K*T, proj_dim], class-major (row k*T + t = template t of class k), as written by
  * mcm_encode_text; bank_dev [K, proj_dim] = normalise(mean over the T templates).  The reference
  * ships the 80 templates (utils/imagenet_templates.py) but never calls them; this is the
- * standard CLIP zero-shot recipe. */
+ * standard CLIP zero-shot recipe.  Stream contract: replayable. */
 int mcm_reduce_bank(mcm_handle* h, const float* feats_dev, int32_t K, int32_t T, float* bank_dev,
                     void* stream);
 
@@ -365,9 +395,10 @@ int mcm_reduce_bank(mcm_handle* h, const float* feats_dev, int32_t K, int32_t T,
  * Scratch (12 bytes per score) is borrowed from the activation workspace mcm_create sized (the B/16
  * batch-512 workspace holds 25 million scores); larger inputs get a one-off stream-ordered allocation
  * (hipMallocAsync / hipFreeAsync on `stream`).
- * STREAM REQUIREMENT: because the scratch is the workspace of the encode / score calls, `stream` must be
- * the stream those calls were issued on (or be ordered after them by an event): stream order is the only
- * thing that keeps mcm_measures from overwriting a tower's activations in flight. */
+ * STREAM REQUIREMENT, an instance of "one stream per handle at a time" (Stream contract, above): because the scratch
+ * is the workspace of the encode / score calls, `stream` must be the stream those calls were issued on (or be ordered
+ * after them by an event): stream order is the only thing that keeps mcm_measures from overwriting a tower's
+ * activations in flight.  Stream contract: synchronising. */
 int mcm_measures(mcm_handle* h, const float* pos_dev, int64_t n_pos, const float* neg_dev,
                  int64_t n_neg, int32_t negate, double recall_level, double* out_host, void* stream);
 
@@ -377,7 +408,7 @@ int mcm_measures(mcm_handle* h, const float* pos_dev, int64_t n_pos, const float
  * semantics (bin i = [e_i, e_{i+1}), last bin closed, out-of-range scores dropped); n_bins <= 8192.
  * As numpy does with explicit bins, -inf, +inf and NaN scores are counted nowhere; repeated edges make
  * zero-width bins that stay empty (a score equal to a repeated LAST edge lands in the last bin).  n == 0 is
- * allowed (scores_dev may then be NULL): all counts are zero. */
+ * allowed (scores_dev may then be NULL): all counts are zero.  Stream contract: replayable. */
 int mcm_score_histogram(mcm_handle* h, const float* scores_dev, int64_t n, const float* edges_dev,
                         int32_t n_bins, int64_t* counts_dev, void* stream);
 
@@ -389,7 +420,8 @@ int mcm_score_histogram(mcm_handle* h, const float* scores_dev, int64_t n, const
  * (:191-198): means_dev [C, proj_dim] fp32 and prec_dev [proj_dim, proj_dim] fp32 are
  * get_mean_prec's classwise_mean and precision; w_dev [C, proj_dim] and k_dev [C] (fp64) are
  * scratch the caller provides, filled by prepare and read by score; scores_dev [B] receives
- * min_c 0.5 (f - mu_c) P (f - mu_c)^T, the value the reference returns per sample. */
+ * min_c 0.5 (f - mu_c) P (f - mu_c)^T, the value the reference returns per sample.
+ * All three entries — Stream contract: replayable. */
 int mcm_encode_image_raw(mcm_handle* h, const float* pixels_dev, int32_t B, float* out_dev, void* stream);
 int mcm_maha_prepare(mcm_handle* h, const float* means_dev, const float* prec_dev, int32_t C,
                      double* w_dev, double* k_dev, void* stream);
@@ -405,9 +437,9 @@ int mcm_maha_score_features(mcm_handle* h, const float* feats_dev, int32_t B, co
  * Every product is rounded once (fma), an element is accumulated row after row in one thread starting from the value
  * already there: no atomics, the same bits on every run and for every split of the rows into calls.  Only the upper
  * triangle of gram_dev is read; the lower one is written as its mirror image, so gram[i][j] == gram[j][i] bit for bit.
- * Asynchronous on `stream`, no allocation, graph-capturable; timed under MCM_KC_SCORE.
+ * Timed under MCM_KC_SCORE.  A replay adds to what gram_dev and sum_dev hold then, as a call does.
  * Refusals (nothing is launched): MCM_EINVAL for a NULL feats_dev / gram_dev / sum_dev or B < 1; MCM_EHIP for a
- * proj_dim beyond 4096, as mcm_maha_score_features. */
+ * proj_dim beyond 4096, as mcm_maha_score_features.  Stream contract: replayable. */
 int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
                             const float* shift_dev /* [proj_dim] or NULL */, double* gram_dev, double* sum_dev,
                             void* stream);
@@ -429,12 +461,11 @@ int mcm_maha_fit_accumulate(mcm_handle* h, const float* feats_dev /* [B, proj_di
  * run (no atomics, nothing summed across workgroups, no workgroup waits for another).
  * mcm_knn_workspace_bytes: *bytes_out = the work_dev size mcm_knn_score_features needs for the same (B, N, k, splits);
  * with splits = 0 it resolves the split count on the CURRENT device, as the score call does.
- * Asynchronous on `stream`, no allocation, no host synchronisation, graph-capturable (after one call outside the
- * capture, which sets the kernels' LDS attribute); timed under MCM_KC_SCORE (2 B N P flop).
+ * Timed under MCM_KC_SCORE (2 B N P flop).
  * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
  * B < 1, N < 1, k outside 1 .. MCM_KNN_MAX_K, splits < 0 or > MCM_KNN_MAX_SPLITS, work_bytes below
  * mcm_knn_workspace_bytes, proj_dim % 4 != 0, or feats_dev / bank_dev not 16-byte aligned (rows are read 16 bytes at a
- * time).  topv_dev may be NULL. */
+ * time).  topv_dev may be NULL.  Stream contract: replayable. */
 #define MCM_KNN_MAX_K 1024
 #define MCM_KNN_MAX_SPLITS 32
 int mcm_knn_workspace_bytes(const mcm_handle* h, int32_t B, int64_t N, int32_t k, int32_t splits, int64_t* bytes_out);
@@ -467,11 +498,11 @@ int mcm_knn_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim
  * across `splits` the sums are associated differently and the results agree to rounding, not bit for bit.
  * mcm_neglabel_workspace_bytes: *bytes_out = the work_dev size the score call needs for the same (B, K, G, gs, splits);
  * with splits = 0 it resolves the split count on the CURRENT device, as the score call does.
- * Asynchronous on `stream`, no allocation, no host synchronisation; timed under MCM_KC_SCORE (2 B N P flop).
+ * Timed under MCM_KC_SCORE (2 B N P flop).
  * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
  * B, K, G or gs < 1, G > MCM_NEG_MAX_GROUPS, T <= 0 or not finite, splits < 0 or > MCM_KNN_MAX_SPLITS, work_bytes below
  * mcm_neglabel_workspace_bytes, proj_dim % 4 != 0, feats_dev / bank_dev not 16-byte aligned, or K + G gs above
- * INT32_MAX.  group_dev may be NULL. */
+ * INT32_MAX.  group_dev may be NULL.  Stream contract: replayable. */
 #define MCM_NEG_MAX_GROUPS 1024
 int mcm_neglabel_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t G, int32_t gs, int32_t splits,
                                  int64_t* bytes_out);
@@ -506,11 +537,11 @@ int mcm_neglabel_score_features(mcm_handle* h, const float* feats_dev /* [B, pro
  * across `splits` the sums are associated differently and the results agree to rounding, not bit for bit.
  * mcm_vim_workspace_bytes: *bytes_out = the work_dev size the score call needs for the same (B, K, R, splits); with
  * splits = 0 it resolves the split count on the CURRENT device, as the score call does.
- * Asynchronous on `stream`, no allocation, no host synchronisation; timed under MCM_KC_SCORE (2 B N P flop).
+ * Timed under MCM_KC_SCORE (2 B N P flop).
  * Refusals (nothing is launched): MCM_EINVAL for a NULL h / feats_dev / bank_dev / work_dev / scores_dev / bytes_out,
  * B, K or R < 1, K + R above INT32_MAX, T <= 0 or not finite, alpha not finite, splits < 0 or > MCM_KNN_MAX_SPLITS,
  * work_bytes below mcm_vim_workspace_bytes, proj_dim % 4 != 0, feats_dev / bank_dev not 16-byte aligned, or off_dev /
- * work_dev not 8-byte aligned.  off_dev and parts_dev may be NULL. */
+ * work_dev not 8-byte aligned.  off_dev and parts_dev may be NULL.  Stream contract: replayable. */
 int mcm_vim_workspace_bytes(const mcm_handle* h, int32_t B, int32_t K, int32_t R, int32_t splits, int64_t* bytes_out);
 int mcm_vim_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim] */, int32_t B,
                            const float* bank_dev /* [K + R, proj_dim]: prompts, then basis rows */, int32_t K, int32_t R,
@@ -534,11 +565,11 @@ int mcm_vim_score_features(mcm_handle* h, const float* feats_dev /* [B, proj_dim
  * B R rows in tiles of 64 that writes the row values to work_dev (B R floats; and to patch_dev when given), one workgroup
  * per image for the maximum.  work_dev needs no initialisation.  The outputs are a pure function of (local_dev, text_dev, T):
  * the same bits on every run, for every cut of the images into calls and for every image position (no atomics, no
- * workgroup waits for another).  Asynchronous on `stream`, no allocation, no host synchronisation; timed under
- * MCM_KC_SCORE (2 B R K P flop).
+ * workgroup waits for another).  Timed under MCM_KC_SCORE (2 B R K P flop).
  * Refusals (nothing is launched): MCM_EINVAL for a NULL h / local_dev / text_dev / work_dev / local_scores_dev / bytes_out,
  * B, R or K < 1, B R above INT32_MAX, T <= 0 or not finite, proj_dim % 4 != 0, local_dev / text_dev not 16-byte aligned
- * (an output not 4-byte aligned), or work_bytes below mcm_local_workspace_bytes.  patch_dev may be NULL. */
+ * (an output not 4-byte aligned), or work_bytes below mcm_local_workspace_bytes.  patch_dev may be NULL.
+ * mcm_local_score_features — Stream contract: replayable. */
 int mcm_local_workspace_bytes(const mcm_handle* h, int32_t B, int32_t R, int32_t K, int64_t* bytes_out);
 int mcm_local_score_features(mcm_handle* h, const float* local_dev /* [B, R, proj_dim] */, int32_t B, int32_t R,
                              const float* text_dev /* [K, proj_dim] */, int32_t K, float T, void* work_dev,
@@ -558,10 +589,11 @@ int mcm_local_score_features(mcm_handle* h, const float* local_dev /* [B, R, pro
  * mcm_score_glmcm: the same, the local rows kept in the handle's workspace; global_scores[b] = -S_G are the bits of
  * mcm_score (MCM_SCORE_MCM) for the same pixels, local_scores / patch the bits of mcm_local_score_features on
  * mcm_encode_image_local's rows, scores[b] = (float)((double) global_scores[b] + (double) lambda (double) local_scores[b]).
- * There is no split-activation (x2) form of either.  Asynchronous on `stream`, no allocation.
+ * There is no split-activation (x2) form of either.
  * Refusals (nothing is launched): those of mcm_encode_image_ex; MCM_EINVAL for a NULL local_dev / text_dev / scores_dev, a
  * local_dev or text_dev not 16-byte aligned, K < 1, T <= 0 or not finite, lambda not finite, proj_dim % 16 != 0 or
- * proj_dim > v_width (the workspace the local pass borrows), a tower without patch tokens. */
+ * proj_dim > v_width (the workspace the local pass borrows), a tower without patch tokens.
+ * Both entries — Stream contract: replayable. */
 int mcm_encode_image_local(mcm_handle* h, const void* pixels_dev, int32_t pixel_format, int32_t B,
                            float* global_dev /* [B, proj_dim], unit-norm */,
                            float* local_dev /* [B, R, proj_dim], unit-norm */, void* stream);
@@ -620,7 +652,7 @@ int mcm_profile_read(mcm_handle* h, double* ms_out, int64_t* launches_out, doubl
  *   1: QuickGELU(acc+bias)          out dtype = operand dtype   (activations.py:117-123)
  *   2: resid[M,N] (fp32) += acc+bias   in place; `y` ignored
  * M ≥ 1 arbitrary (ragged tiles are clamped/masked); K % 64 == 0 (bf16) or K % 32 == 0
- * (fp32): one K-step is 128 bytes per row; N % 16 == 0. */
+ * (fp32): one K-step is 128 bytes per row; N % 16 == 0.  Stream contract: replayable. */
 int mcm_op_linear(mcm_handle* h, int32_t prec, const void* x_dev, const void* w_dev,
                   const float* bias_dev, void* y_dev, float* resid_dev, int32_t M, int32_t N,
                   int32_t K, int32_t epi, void* stream);
@@ -634,23 +666,25 @@ int mcm_op_linear(mcm_handle* h, int32_t prec, const void* x_dev, const void* w_
 #define MCM_LINEAR_SPLIT_X 2
 #define MCM_LINEAR_SPLIT_OUT 4
 /* bit 3 (ABI 5; epilogue 1 only, every mode): the activation is the exact erf GELU (MCM_ACT_GELU) instead of QuickGELU — the
- * fc1 epilogue of a tower whose hidden_act is "gelu".  Combines with the three bits above exactly as epilogue 1 does. */
+ * fc1 epilogue of a tower whose hidden_act is "gelu".  Combines with the three bits above exactly as epilogue 1 does.
+ * mcm_op_linear_ex — Stream contract: replayable. */
 #define MCM_LINEAR_ACT_GELU 8
 int mcm_op_linear_ex(mcm_handle* h, int32_t prec, const void* x_dev, const void* w_dev,
                      const float* bias_dev, void* y_dev, float* resid_dev, int32_t M, int32_t N,
                      int32_t K, int32_t epi, int32_t flags, void* stream);
-/* fp32 w [N,K] (device) → split operand image [N, 2K] in the 16-bit dtype of `prec` (K % 64 == 0). */
+/* fp32 w [N,K] (device) → split operand image [N, 2K] in the 16-bit dtype of `prec` (K % 64 == 0).
+ * Stream contract: replayable. */
 int mcm_op_split_weight(mcm_handle* h, int32_t prec, const float* w_dev, int32_t N, int32_t K,
                         void* out_dev, void* stream);
 /* LayerNorm over the last dim (modeling_clip.py:370,379,605,608): x fp32 [M,D] →
- * y (operand dtype of `prec`, or fp32 when out_f32 != 0) [M,D]. */
+ * y (operand dtype of `prec`, or fp32 when out_f32 != 0) [M,D].  Stream contract: replayable. */
 int mcm_op_layernorm(mcm_handle* h, int32_t prec, const float* x_dev, const float* gamma_dev,
                      const float* beta_dev, void* y_dev, int32_t M, int32_t D, float eps,
                      int32_t out_f32, void* stream);
 /* The split-activation arm's LayerNorm and attention (fp16): y [M, 2D] / out [rows, 2 heads 64] are split images (per 64
  * columns hi[64] then lo[64]); mcm_op_attention_split reads qkv as a split image [rows, 6 heads 64].  head_dim 64; the
  * model's vision tower also runs head_dim 80 (ViT-H/14), which the operator level reaches through the harness library's
- * mcm_debug_op_attention_split_hd. */
+ * mcm_debug_op_attention_split_hd.  Both entries — Stream contract: replayable. */
 int mcm_op_layernorm_split(mcm_handle* h, const float* x_dev, const float* gamma_dev, const float* beta_dev,
                            void* y_dev, int32_t M, int32_t D, float eps, void* stream);
 int mcm_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, int32_t nseq, int32_t seq_len,
@@ -664,7 +698,7 @@ int mcm_op_attention_split(mcm_handle* h, const void* qkv_dev, void* out_dev, in
  *   seq_len 289 ... 1025, bidirectional only: K and V streamed through LDS in 64-key tiles with an online softmax (every mode,
  *   mcm_op_attention_split too; ViT-L/14@336px: 577 tokens).
  * A bidirectional seq_len above 1025 (the vision-token ceiling of mcm_create) is refused; causal attention (the text tower's
- * 77 tokens) has the first route only. */
+ * 77 tokens) has the first route only.  Stream contract: replayable. */
 int mcm_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out_dev,
                      int32_t nseq, int32_t seq_len, int32_t heads, int32_t causal,
                      void* stream);
@@ -677,7 +711,8 @@ int mcm_op_attention(mcm_handle* h, int32_t prec, const void* qkv_dev, void* out
  * mcm_saturation_count: *count_host = events since the last reset (0 = no activation of any call left the fp16
  * range); synchronises `stream`; reset != 0 clears the counter.  mcm_saturation_check(h, 0) stops the kernels
  * from reporting (the tracking itself is a handful of VALU instructions per tile and is always compiled in).
- * Always 0 in MCM_PREC_BF16 / MCM_PREC_F32 (fp32 exponent range). */
+ * Always 0 in MCM_PREC_BF16 / MCM_PREC_F32 (fp32 exponent range).
+ * mcm_saturation_count — Stream contract: synchronising. */
 int mcm_saturation_check(mcm_handle* h, int32_t on);
 int mcm_saturation_count(mcm_handle* h, int32_t reset, uint64_t* count_host, void* stream);
 

@@ -43,14 +43,14 @@ extern "C" {
  * and the results agree to rounding, not bit for bit (max-logit and idx_dev do not depend on it).
  * mcm_score_stream_workspace_bytes: *bytes_out = the work_dev size the score call needs for the same (B, K, topk, splits);
  * with splits = 0 it resolves the split count on the CURRENT device, as the score call does.
- * Asynchronous on `stream`, no allocation, no host synchronisation, graph-capturable (after one call outside the capture,
- * which sets the kernels' LDS attribute); timed under MCM_KC_SCORE (2 B K P flop).
+ * Timed under MCM_KC_SCORE (2 B K P flop).
  * Refusals (nothing is launched): MCM_EINVAL for a NULL h / img_feat_dev / text_feat_dev / work_dev / scores_dev / bytes_out,
  * B or K < 1, K above INT32_MAX (rows are numbered in int32), T <= 0 or not finite, kind outside MCM_SCORE_MCM ..
  * MCM_SCORE_VAR, topk outside 0 .. MCM_TOPK_MAX, a NULL idx_dev with topk > 0, splits < 0 or > MCM_KNN_MAX_SPLITS, work_bytes
  * below mcm_score_stream_workspace_bytes, proj_dim % 4 != 0, img_feat_dev / text_feat_dev not 16-byte aligned, or work_dev
  * not 8-byte aligned.  parts_dev and prob_dev may be NULL; idx_dev and prob_dev are not touched with topk = 0.
- * From pixels: mcm_encode_image_ex(normalize = 1) (or mcm_encode_image_x2) into a buffer of the caller's, then this call. */
+ * From pixels: mcm_encode_image_ex(normalize = 1) (or mcm_encode_image_x2) into a buffer of the caller's, then this call.
+ * mcm_score_features_stream — Stream contract: replayable (the classes: include/mcm.h, "Stream contract"). */
 int mcm_score_stream_workspace_bytes(const mcm_handle* h, int32_t B, int64_t K, int32_t topk, int32_t splits,
                                      int64_t* bytes_out);
 int mcm_score_features_stream(mcm_handle* h, const float* img_feat_dev /* [B, proj_dim] */, int32_t B,
